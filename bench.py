@@ -17,11 +17,18 @@ computes its shard partial (Fp12 Miller product + G2 sum, 864 B), the partials a
 all-gathered over RCCL, and the combined check runs on the gathered partials (weak scaling:
 4096 votes per GPU).
 
-Also reported: "roofline" for the dominant kernel stage (integer VALU: 32x32-bit MAC lane-op
-rate from the work model in consensus_overlord_amd/workmodel.json over HIP-event time on the
-library's stream, against the microbenchmarked v_mad_u64_u32 rate), and "cpu_baseline" (the
-C restatement of the CPU oracle, timed on rank 0 at N = 1: RLC batch on the host threads
-plus the serial per-vote call shape on a bounded prefix).
+A plain run sets up, warms up, times --steps batches and prints the result line (metric, value,
+ms_per_step, ...). --dump-outputs DIR also writes the last timed batch's per-vote verdict codes
+to DIR/codes.npy and the device-made signatures and public keys it verified to DIR/sigs.npy and
+DIR/pks.npy (float32; the inputs are seeded, so two builds can be compared value for value).
+
+With --full also reported: "roofline" for the dominant kernel stage (integer VALU: 32x32-bit MAC
+lane-op rate from the work model in consensus_overlord_amd/workmodel.json over HIP-event time on
+the library's stream, against the microbenchmarked v_mad_u64_u32 rate), "stage_ms" and
+"batch_latency_ms" (untimed unpipelined profile batches), the vote kernel's held clock, "latency"
+(the per-call and small-batch probes) and "cpu_baseline" (the C restatement of the CPU oracle,
+timed on rank 0 at N = 1: RLC batch on the host threads plus the serial per-vote call shape on a
+bounded prefix).
 """
 from __future__ import annotations
 
@@ -426,6 +433,134 @@ def vote_clock(sigs, hs, pks, seconds: float):
                      "x 100 MHz after back-to-back batches (OVH_FLAG_VM_CLOCK diagnostic context)"}
 
 
+def roofline(B: int, world: int, value: float, names, avg_ms, vote_spans, clock):
+    """--full: the roofline of the dominant kernel stage and the per-stage times, from the profile
+    batches' mean stage times avg_ms, the timed batches' vote_spans and the held-clock pass."""
+    nst = len(names)
+    with open(os.path.join(ROOT, "consensus_overlord_amd", "workmodel.json")) as fh:
+        wm = json.load(fh)
+    macs_per_M = wm["macs_per_M"]
+    Mu = wm["M_per_unit"]
+    stages = {names[k]: round(float(avg_ms[k]), 4) for k in range(nst)}
+    dom = max((k for k in range(nst) if names[k] in STAGE_TO_WORK), key=lambda k: avg_ms[k])
+    dname = names[dom]
+    units = 1 if dname in PER_BATCH_STAGES else B
+    # the vote pool's committed PMC passes (tools/pmc_pool.sh -> tools/pmc_pool_summary.py):
+    # HBM bytes per 4,096-vote batch (FETCH_SIZE doubled per the gfx950 correction) and the
+    # instruction counts per quad for the counter decomposition below; null if absent
+    pmc = None
+    ppath = os.path.join(ROOT, "consensus_overlord_amd", "pmc_pool.json")
+    if os.path.exists(ppath):
+        with open(ppath) as fh:
+            pmc = json.load(fh)
+    traffic = pmc["hbm_bytes_per_batch"] if (pmc and dname == "vote" and B == 4096) else None
+    # algorithmic work of the dominant stage: SURVEY.md 8(d) canonical W_v = 18,300 M per vote
+    # (Appendix C) less the Pippenger MSM share (350 M), the Fp12 merge (54 M) and the
+    # amortised final exponentiation (4 M), which other kernels do; the program's own count
+    # (vote program) is reported beside it, and the MSM kernels' own fraction below
+    canon = {"vote": W_V_CANON - W_MSM - 54 - 4}
+    work_M = canon.get(dname, Mu[STAGE_TO_WORK[dname]])
+    macs = work_M * units * macs_per_M
+    # the vote pool's device time per batch over the timed region (vote_spans: the union of
+    # the pool streams' HIP-event spans / batches) when recorded, else the unpipelined profile
+    # batches' HIP-event stage time
+    kern_ms = vote_spans["device_ms_per_launch"] if (dname == "vote" and vote_spans) else avg_ms[dom]
+    achieved = macs / (kern_ms * 1e-3) / 1e12
+    prog_achieved = Mu[STAGE_TO_WORK[dname]] * units * macs_per_M / (kern_ms * 1e-3) / 1e12
+    path_M = W_V_CANON
+    held = clock["clock_ghz"] if clock else None
+    # counter decomposition of frac (VERDICT r04 item 3): frac = VALU busy x v_mad share x
+    # useful MACs per issued v_mad lane-op x (4.14 / 4 cycles per v_mad at the peak's rate) x
+    # (clock / the peak's clock); VALU busy from the PMC instruction count per quad and this
+    # run's time per batch, 1,024 SIMDs at the held clock (2.371 GHz without the clock pass)
+    decomp = None
+    if pmc and dname == "vote" and B == 4096 and pmc.get("valu_per_quad"):
+        ghz = held or PEAK_MAD_U64_CLOCK_GHZ
+        quads = B // 4
+        busy = quads * pmc["valu_per_quad"] * 4 / (1024 * ghz * 1e9 * kern_ms * 1e-3)
+        mad_share = pmc["mad_per_quad_static"] / pmc["valu_per_quad"]
+        lane_use = 4 * work_M * macs_per_M / (pmc["mad_per_quad_static"] * 64)
+        issue = 4.14 / 4 * ghz / PEAK_MAD_U64_CLOCK_GHZ
+        pred = busy * mad_share * lane_use * issue
+        decomp = {"valu_busy": round(busy, 4), "mad_share": round(mad_share, 4), "lane_use": round(lane_use, 4),
+                  "issue_factor": round(issue, 4), "product": round(pred, 4),
+                  "product_over_frac": round(pred / (achieved * 1e12 / PEAK_MAD_U64), 4),
+                  "valu_per_quad": pmc["valu_per_quad"], "mad_per_quad": pmc["mad_per_quad_static"],
+                  "lanes_per_valu": pmc.get("lanes_per_valu"),
+                  "wait_any_share": pmc.get("wait_any_share"), "wait_basis": pmc.get("wait_basis"),
+                  "lds_bank_conflict_share": pmc.get("lds_bank_conflict_share"),
+                  "write_kb_per_batch": pmc.get("write_kb_per_batch"),
+                  "basis": "valu_busy = 1,024 quads x SQ_INSTS_VALU per quad x 4 cycles / (1,024 SIMDs x clock x "
+                           "kernel_ms_per_batch); mad_share = static v_mad_u64_u32 per quad / SQ_INSTS_VALU per "
+                           "quad; lane_use = algorithmic MACs per quad / (v_mad per quad x 64 lanes); "
+                           "issue_factor = 4.14 / 4 x clock / 2.371 GHz (the peak's measured v_mad rate); "
+                           "counters: " + pmc["source"]}
+    roof = {
+        "bound": "valu",
+        "kernel": dname,
+        "achieved": round(achieved, 3),
+        "kernel_ms_per_batch": round(float(kern_ms), 4),
+        "time_basis": ("the vote pool's device time per batch: union over the timed batches of the HIP-event "
+                       "spans around each batch's pool grids on the two pool streams, / batches (the grids "
+                       "are persistent: a batch's span runs from its grids' launch point on the pool streams "
+                       "to their exit, and consecutive spans overlap; launch_ms = the mean span)"
+                       if (dname == "vote" and vote_spans)
+                       else "HIP-event stage time of the unpipelined profile batches"),
+        "vote_spans": vote_spans,
+        "peak": round(PEAK_MAD_U64 / 1e12, 3),
+        "unit": "TOP/s (32x32-bit integer MAC lane-ops; peak = measured v_mad_u64_u32 rate)",
+        "frac": round(achieved * 1e12 / PEAK_MAD_U64, 4),
+        "peak_basis": "v_mad_u64_u32 lane-op rate measured by tools/ubench/int_rates.hip at its best "
+                      "occupancy (profiles/r04_int_rates.json), at the clock that run held (%s GHz)"
+                      % (PEAK_MAD_U64_CLOCK_GHZ,),
+        "peak_fullrate": round(PEAK_FULLRATE / 1e12, 3),
+        "frac_of_fullrate_valu": round(achieved * 1e12 / PEAK_FULLRATE, 4),
+        "fullrate_basis": "SURVEY 8(d): 256 CU x 64 lanes/clk x 2.4 GHz (one wave instruction per 4 "
+                          "cycles per SIMD)",
+        "vote_clock": clock,
+        "frac_of_fullrate_at_held_clock": (round(achieved * 1e12 / (256 * 64 * held * 1e9), 4)
+                                           if held else None),
+        "frac_of_1wave_chain_rate": round(achieved * 1e12 / PEAK_MAD_1WAVE_CHAIN, 4),
+        "one_wave_chain_basis": "v_mad_u64_u32 on one dependent chain at one wave per SIMD (the vote "
+                                "kernel's occupancy and the product's order), 2.6448e13 lane-ops/s",
+        "work_M_per_unit": work_M,
+        "work_basis": "SURVEY 8(d) canonical W_v minus MSM + merge + amortised FE" if dname in canon
+                      else "program heavy ops (workmodel.json)",
+        "program_M_per_unit": Mu[STAGE_TO_WORK[dname]],
+        "program_frac": round(prog_achieved * 1e12 / PEAK_MAD_U64, 4),
+        "traffic": traffic,
+        "traffic_unit": "HBM bytes per 4,096-vote batch of the vote pool (PMC FETCH_SIZE x 2 + WRITE_SIZE, "
+                        "consensus_overlord_amd/pmc_pool.json)",
+        "pmc": decomp,
+        "msm": ({"ms": round(float(avg_ms[names.index("msm")]), 4), "work_M_per_unit": W_MSM,
+                 "frac": round(W_MSM * B * macs_per_M / (avg_ms[names.index("msm")] * 1e-3) / PEAK_MAD_U64, 4)}
+                if avg_ms[names.index("msm")] > 0 else None),
+        "path_M_per_vote": round(path_M, 1),
+        "path_frac": round(value / world * path_M * macs_per_M / PEAK_MAD_U64, 4),
+    }
+    return roof, stages
+
+
+DUMP_BYTES = 64 << 20   # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path: str, codes, sigs, pks, suffix: str = "") -> None:
+    """--dump-outputs: path/<name><suffix>.npy in float32, one row per vote:
+      codes  what the caller of the timed path receives from the last timed step: that batch's
+             per-vote verdict codes (int32 on the device; 0 = valid, so all zero on this workload)
+      sigs, pks  the votes that step verified: the 96-byte signatures and 48-byte public keys the
+             library's sign / key kernels made from the seeded secret keys (the byte values)
+    A batch too large for DUMP_BYTES is written as a fixed seeded sample of its votes, the same
+    rows in every array and every run."""
+    arrs = {"codes": np.asarray(codes), "sigs": np.asarray(sigs), "pks": np.asarray(pks)}
+    n = len(arrs["codes"])
+    keep = DUMP_BYTES // (4 * sum(a[0].size for a in arrs.values())) if n else 0
+    rows = np.sort(np.random.default_rng(SEED).choice(n, keep, replace=False)) if n > keep else None
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + suffix + ".npy"), (a if rows is None else a[rows]).astype(np.float32))
+
+
 def multi_device_leg(args) -> None:
     """One process over several GPUs through the C ABI alone (ovh_create_multi +
     ovh_verify_batch_async + ovh_batch_wait): what a node linking libovhip.so without torch
@@ -457,6 +592,8 @@ def multi_device_leg(args) -> None:
     elapsed = time.perf_counter() - t0
     if any((o != 0).any() for o in outs):
         raise RuntimeError("multi-device batches rejected valid votes")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs[-1], sigs, pks)
     print(json.dumps({
         "metric": "BLS12-381 vote verifications/sec (batch 4096) at 1/2/4/8 MI355X vs host blst",
         "value": round(n * args.steps / elapsed, 2), "unit": "verifications/s", "n_gpus": len(set(devs)),
@@ -477,6 +614,14 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=4096, help="votes per GPU per step")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last timed batch's per-vote verdict codes to "
+                         "DIR/codes.npy and the device-made votes it verified to DIR/sigs.npy and DIR/pks.npy "
+                         "(float32; <name>_rank<r>.npy per rank at --gpus > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the untimed legs: profile batches (stage_ms, "
+                         "batch_latency_ms, roofline), the held-clock pass, the latency probes and the CPU "
+                         "baseline; the options below down to --clock-seconds shape those legs")
     ap.add_argument("--profile-steps", type=int, default=3, help="untimed unpipelined batches for stage times")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -531,7 +676,8 @@ def main():
     hs = torch.from_numpy(hs_h).cuda()
     pks = dev.sk_to_pk_batch(ctx, sks)
     sigs = dev.sign_batch(ctx, sks, hs)
-    nbatch = args.warmup + args.steps + args.profile_steps
+    profile_steps = args.profile_steps if args.full else 0
+    nbatch = args.warmup + args.steps + profile_steps
     codes = torch.full((nbatch, B), -1, dtype=torch.int32, device="cuda")   # one verdict row per batch
     shards = ShardVerifier(DeviceBackend(ctx)) if sharded else None
     # the timed batches' context: the profiling one (HIP events around each batch's pool grids
@@ -622,69 +768,14 @@ def main():
     bad = int((codes != 0).sum().item())
     if bad:
         raise RuntimeError("batch verify rejected %d valid votes" % bad)
-    clock = vote_clock(sigs, hs, pks, args.clock_seconds) if (rank == 0 and args.clock_seconds > 0) else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, codes[args.warmup + args.steps - 1].cpu().numpy(), sigs.cpu().numpy(),
+                     pks.cpu().numpy(), "" if world == 1 else "_rank%d" % rank)
+    clock = vote_clock(sigs, hs, pks, args.clock_seconds) \
+        if (args.full and rank == 0 and args.clock_seconds > 0) else None
 
     if rank == 0:
-        with open(os.path.join(ROOT, "consensus_overlord_amd", "workmodel.json")) as fh:
-            wm = json.load(fh)
-        macs_per_M = wm["macs_per_M"]
-        Mu = wm["M_per_unit"]
-        avg_ms = stage_ms / max(1, args.profile_steps)
-        stages = {names[k]: round(float(avg_ms[k]), 4) for k in range(nst)}
-        dom = max((k for k in range(nst) if names[k] in STAGE_TO_WORK), key=lambda k: avg_ms[k])
-        dname = names[dom]
-        units = 1 if dname in PER_BATCH_STAGES else B
-        # the vote pool's committed PMC passes (tools/pmc_pool.sh -> tools/pmc_pool_summary.py):
-        # HBM bytes per 4,096-vote batch (FETCH_SIZE doubled per the gfx950 correction) and the
-        # instruction counts per quad for the counter decomposition below; null if absent
-        pmc = None
-        ppath = os.path.join(ROOT, "consensus_overlord_amd", "pmc_pool.json")
-        if os.path.exists(ppath):
-            with open(ppath) as fh:
-                pmc = json.load(fh)
-        traffic = pmc["hbm_bytes_per_batch"] if (pmc and dname == "vote" and B == 4096) else None
-        # algorithmic work of the dominant stage: SURVEY.md 8(d) canonical W_v = 18,300 M per vote
-        # (Appendix C) less the Pippenger MSM share (350 M), the Fp12 merge (54 M) and the
-        # amortised final exponentiation (4 M), which other kernels do; the program's own count
-        # (vote program) is reported beside it, and the MSM kernels' own fraction below
-        canon = {"vote": W_V_CANON - W_MSM - 54 - 4}
-        work_M = canon.get(dname, Mu[STAGE_TO_WORK[dname]])
-        macs = work_M * units * macs_per_M
-        # the vote pool's device time per batch over the timed region (vote_spans: the union of
-        # the pool streams' HIP-event spans / batches) when recorded, else the unpipelined profile
-        # batches' HIP-event stage time
-        kern_ms = vote_spans["device_ms_per_launch"] if (dname == "vote" and vote_spans) else avg_ms[dom]
-        achieved = macs / (kern_ms * 1e-3) / 1e12
-        prog_achieved = Mu[STAGE_TO_WORK[dname]] * units * macs_per_M / (kern_ms * 1e-3) / 1e12
         value = world * B * args.steps / elapsed
-        path_M = W_V_CANON
-        held = clock["clock_ghz"] if clock else None
-        # counter decomposition of frac: frac = VALU busy x v_mad share x
-        # useful MACs per issued v_mad lane-op x (4.14 / 4 cycles per v_mad at the peak's rate) x
-        # (clock / the peak's clock); VALU busy from the PMC instruction count per quad and this
-        # run's time per batch, 1,024 SIMDs at the held clock (2.371 GHz without the clock pass)
-        decomp = None
-        if pmc and dname == "vote" and B == 4096 and pmc.get("valu_per_quad"):
-            ghz = held or PEAK_MAD_U64_CLOCK_GHZ
-            quads = B // 4
-            busy = quads * pmc["valu_per_quad"] * 4 / (1024 * ghz * 1e9 * kern_ms * 1e-3)
-            mad_share = pmc["mad_per_quad_static"] / pmc["valu_per_quad"]
-            lane_use = 4 * work_M * macs_per_M / (pmc["mad_per_quad_static"] * 64)
-            issue = 4.14 / 4 * ghz / PEAK_MAD_U64_CLOCK_GHZ
-            pred = busy * mad_share * lane_use * issue
-            decomp = {"valu_busy": round(busy, 4), "mad_share": round(mad_share, 4), "lane_use": round(lane_use, 4),
-                      "issue_factor": round(issue, 4), "product": round(pred, 4),
-                      "product_over_frac": round(pred / (achieved * 1e12 / PEAK_MAD_U64), 4),
-                      "valu_per_quad": pmc["valu_per_quad"], "mad_per_quad": pmc["mad_per_quad_static"],
-                      "lanes_per_valu": pmc.get("lanes_per_valu"),
-                      "wait_any_share": pmc.get("wait_any_share"), "wait_basis": pmc.get("wait_basis"),
-                      "lds_bank_conflict_share": pmc.get("lds_bank_conflict_share"),
-                      "write_kb_per_batch": pmc.get("write_kb_per_batch"),
-                      "basis": "valu_busy = 1,024 quads x SQ_INSTS_VALU per quad x 4 cycles / (1,024 SIMDs x clock x "
-                               "kernel_ms_per_batch); mad_share = static v_mad_u64_u32 per quad / SQ_INSTS_VALU per "
-                               "quad; lane_use = algorithmic MACs per quad / (v_mad per quad x 64 lanes); "
-                               "issue_factor = 4.14 / 4 x clock / 2.371 GHz (the peak's measured v_mad rate); "
-                               "counters: " + pmc["source"]}
         line = {
             "metric": "BLS12-381 vote verifications/sec (batch 4096) at 1/2/4/8 MI355X vs host blst",
             "value": round(value, 2),
@@ -704,61 +795,20 @@ def main():
                                        + (", persistent pool leaving 8 CUs to the collective" if reserve
                                           else ", a pool grid per batch")) if shards is not None
                        else "single GPU"},
-            "roofline": {
-                "bound": "valu",
-                "kernel": dname,
-                "achieved": round(achieved, 3),
-                "kernel_ms_per_batch": round(float(kern_ms), 4),
-                "time_basis": ("the vote pool's device time per batch: union over the timed batches of the HIP-event "
-                               "spans around each batch's pool grids on the two pool streams, / batches (the grids "
-                               "are persistent: a batch's span runs from its grids' launch point on the pool streams "
-                               "to their exit, and consecutive spans overlap; launch_ms = the mean span)"
-                               if (dname == "vote" and vote_spans)
-                               else "HIP-event stage time of the unpipelined profile batches"),
-                "vote_spans": vote_spans,
-                "peak": round(PEAK_MAD_U64 / 1e12, 3),
-                "unit": "TOP/s (32x32-bit integer MAC lane-ops; peak = measured v_mad_u64_u32 rate)",
-                "frac": round(achieved * 1e12 / PEAK_MAD_U64, 4),
-                "peak_basis": "v_mad_u64_u32 lane-op rate measured by tools/ubench/int_rates.hip at its best "
-                              "occupancy (profiles/r04_int_rates.json), at the clock that run held (%s GHz)"
-                              % (PEAK_MAD_U64_CLOCK_GHZ,),
-                "peak_fullrate": round(PEAK_FULLRATE / 1e12, 3),
-                "frac_of_fullrate_valu": round(achieved * 1e12 / PEAK_FULLRATE, 4),
-                "fullrate_basis": "SURVEY 8(d): 256 CU x 64 lanes/clk x 2.4 GHz (one wave instruction per 4 "
-                                  "cycles per SIMD)",
-                "vote_clock": clock,
-                "frac_of_fullrate_at_held_clock": (round(achieved * 1e12 / (256 * 64 * held * 1e9), 4)
-                                                   if held else None),
-                "frac_of_1wave_chain_rate": round(achieved * 1e12 / PEAK_MAD_1WAVE_CHAIN, 4),
-                "one_wave_chain_basis": "v_mad_u64_u32 on one dependent chain at one wave per SIMD (the vote "
-                                        "kernel's occupancy and the product's order), 2.6448e13 lane-ops/s",
-                "work_M_per_unit": work_M,
-                "work_basis": "SURVEY 8(d) canonical W_v minus MSM + merge + amortised FE" if dname in canon
-                              else "program heavy ops (workmodel.json)",
-                "program_M_per_unit": Mu[STAGE_TO_WORK[dname]],
-                "program_frac": round(prog_achieved * 1e12 / PEAK_MAD_U64, 4),
-                "traffic": traffic,
-                "traffic_unit": "HBM bytes per 4,096-vote batch of the vote pool (PMC FETCH_SIZE x 2 + WRITE_SIZE, "
-                                "consensus_overlord_amd/pmc_pool.json)",
-                "pmc": decomp,
-                "msm": ({"ms": round(float(avg_ms[names.index("msm")]), 4), "work_M_per_unit": W_MSM,
-                         "frac": round(W_MSM * B * macs_per_M / (avg_ms[names.index("msm")] * 1e-3) / PEAK_MAD_U64, 4)}
-                        if avg_ms[names.index("msm")] > 0 else None),
-                "path_M_per_vote": round(path_M, 1),
-                "path_frac": round(value / world * path_M * macs_per_M / PEAK_MAD_U64, 4),
-            },
-            "stage_ms": stages,
-            "batch_latency_ms": round(float(np.median(lat)) * 1e3, 3) if lat else None,
             "enqueue_ms_per_step": round(enqueue_s / args.steps * 1e3, 4),
             "pipelined": "the vote pool runs every batch's per-vote work (persistent grids, quads claimed across "
                          "batches); batch k's fold, MSM, combined check and bisection run on one of four final "
                          "streams beside later batches' votes; all %d timed batches complete inside the timed "
                          "region" % args.steps,
         }
-        if world == 1 and not args.no_latency:
-            line["latency"] = latencies(ctx, sigs, hs, pks)
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(sigs.cpu().numpy(), hs_h, pks.cpu().numpy(), args.cpu_seconds)
+        if args.full:
+            line["roofline"], line["stage_ms"] = roofline(B, world, value, names, stage_ms / max(1, profile_steps),
+                                                          vote_spans, clock)
+            line["batch_latency_ms"] = round(float(np.median(lat)) * 1e3, 3) if lat else None
+            if world == 1 and not args.no_latency:
+                line["latency"] = latencies(ctx, sigs, hs, pks)
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(sigs.cpu().numpy(), hs_h, pks.cpu().numpy(), args.cpu_seconds)
         print(json.dumps(line), flush=True)
     if tctx is not ctx:
         tctx.close()

@@ -5,7 +5,7 @@
 #   POOL=1    tools/pool_probe.py (the vote pool alone)
 #   TESTS=1   pytest -m gpu (TESTS_K: a -k expression)
 #   SMOKE=1   __graft_entry__.smoke()
-#   BENCH=1   bench.py --steps $STEPS (BENCH_ARGS appended)
+#   BENCH=1   bench.py --full --steps $STEPS (BENCH_ARGS appended)
 #   PROF=1    rocprofv3 --kernel-trace --stats over a short bench
 #   PMC=1     tools/pmc_pool.sh (the vote pool's counter passes, one run each; then
 #             python tools/pmc_pool_summary.py $TAG on the CPU side)
@@ -27,7 +27,7 @@ if [ -n "${SMOKE:-}" ]; then
   timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
 fi
 if [ -n "${BENCH:-}" ]; then
-  timeout -k 10 400 python -u bench.py --steps "$STEPS" --warmup 2 ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1
+  timeout -k 10 400 python -u bench.py --full --steps "$STEPS" --warmup 2 ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1
 fi
 if [ -n "${PROF:-}" ]; then
   cd /tmp

@@ -14,7 +14,7 @@ if [ -n "${TESTS:-}" ]; then
 fi
 for r in $(seq 1 ${ROUNDS:-2}); do
   for lib in libovhip.so ${LIBS}; do
-    OVH_LIBPATH=$R/consensus_overlord_amd/$lib timeout -k 10 200 python -u bench.py --steps ${STEPS:-30} --warmup 2 \
+    OVH_LIBPATH=$R/consensus_overlord_amd/$lib timeout -k 10 200 python -u bench.py --full --steps ${STEPS:-30} --warmup 2 \
       --no-cpu-baseline $([ -n "${LAT:-}" ] && echo --profile-steps 1 || echo --no-latency) > "$OUT/bench_${lib%.so}_$r.log" 2>&1
     echo "$lib $r $(python -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); print(d['value'], d['ms_per_step'], d['stage_ms'], d.get('latency', ''))" "$OUT/bench_${lib%.so}_$r.log")" >> "$OUT/summary.txt"
   done

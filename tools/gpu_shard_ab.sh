@@ -17,7 +17,7 @@ fi
 run() {  # name, env, bench args
   local name=$1 envs=$2
   shift 2
-  env $envs timeout -k 10 200 python -u bench.py --steps ${STEPS:-30} --warmup 2 --no-cpu-baseline --no-latency \
+  env $envs timeout -k 10 200 python -u bench.py --full --steps ${STEPS:-30} --warmup 2 --no-cpu-baseline --no-latency \
     --clock-seconds 0 "$@" > "$OUT/bench_${name}_$r.log" 2>&1
   echo "$name $r $(python -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); print(d['value'], d['ms_per_step'], d['stage_ms'])" "$OUT/bench_${name}_$r.log")" >> "$OUT/summary.txt"
 }
