@@ -8,16 +8,21 @@
 // digit d = byte w of its scalar lands in bucket w * 255 + d - 1 (d = 0: nothing).
 //
 //   k_msm_count    lane per vote: bucket histogram in LDS, then one global add per bucket
-//   k_msm_scan     one wave: bucket offsets, and per tree level the prefix of the bucket's
-//                  pair counts (the level kernels' work lists)
+//   k_msm_scan     one wave: bucket offsets, the prefix of the buckets' level-0 pair counts
+//                  (where a bucket's tree lives in A) and of their chunk counts (k_msm_chunk's
+//                  work list)
 //   k_msm_scatter  lane per vote: point ids into their bucket's range (counting sort)
-//   k_msm_pair     the VM pair kernels (8- or 16-lane slices, Fp-VM slots in LDS hold the
-//                  bucket accumulators): bucket tree level 0 (madd, affine points), levels >= 1
-//                  (padd, in place), bit-plane sums T_t = sum of the buckets whose digit has bit
-//                  t % 8 set, window combination sum_t 2^t T_t (hdbl<m>: A + [2^m] B)
+//   the VM pair kernels (8- or 16-lane slices, Fp-VM slots in LDS hold the operands), each
+//   running several tree levels inside its one-wave workgroups:
+//   k_msm_chunk    bucket tree levels 0 (madd, affine points) to 5 (padd, in place) of one
+//                  64-entry chunk of a bucket
+//   k_msm_upper    bucket tree levels >= 6 of one bucket (more than 64 points in it)
+//   k_msm_plane    bit-plane sums T_t = sum of the buckets whose digit has bit t % 8 set
+//   k_msm_comb     window combination sum_t 2^t T_t (hdbl<m>: A + [2^m] B)
 // Buckets are summed as trees over the sorted entries (entry k of bucket b absorbs k + 2^l at
-// level l), so a bucket of c points needs ceil(log2 c) levels and no sequential chain; the
-// host launches the worst case's levels and the device exits the empty ones.
+// level l), so a bucket of c points needs ceil(log2 c) levels and no sequential chain. Ten
+// launches per batch (nine up to 32 votes); tests/test_msm_chunk_model.py restates which
+// workgroup runs which pair.
 #pragma once
 
 #define MSM_NBW 255                 // buckets per window (digits 1..255)
@@ -26,11 +31,14 @@
 #define MSM_TM 64                   // pairs of a target's level-0 sum (128 member buckets)
 #define MSM_LV 27                   // bucket tree levels (2^26 >= 2 x 2^24 points in one bucket)
 #define MSM_U (MSM_NT * MSM_TM)     // U plane entries
+#define MSM_CH_LV 6                 // bucket tree levels that k_msm_chunk runs in one workgroup
+#define MSM_CH (1u << MSM_CH_LV)    // entries of a chunk
+#define MSM_PF_ROWS 2               // prefix rows: level-0 pairs, chunks
 
 struct MsmArgs {
   const uint32_t* cnt;  // NB: points per bucket
   const uint32_t* off;  // NB + 1: first sorted entry of each bucket
-  const uint32_t* pf;   // MSM_LV x (NB + 1): prefix of the per-bucket pair counts per level
+  const uint32_t* pf;   // MSM_PF_ROWS x (NB + 1): prefix of the buckets' level-0 pairs, of their chunks
   const uint32_t* ent;  // sorted entries: point id 2 i + h (h = 1: tau of vote i)
   Slab st;              // vote state (sigma / tau planes)
   Slab A;               // bucket trees: entry k of bucket b (k even) at pf[0][b] + k / 2
@@ -100,24 +108,22 @@ __device__ __forceinline__ uint32_t wave_scan_nb(F v, G out) {
   return __shfl(incl, 63, 64);
 }
 
-__global__ __launch_bounds__(64) void k_msm_scan(uint32_t nlev, const uint32_t* __restrict__ cnt,
-                                                 uint32_t* __restrict__ off, uint32_t* __restrict__ cur,
-                                                 uint32_t* __restrict__ pf) {
+__global__ __launch_bounds__(64) void k_msm_scan(const uint32_t* __restrict__ cnt, uint32_t* __restrict__ off,
+                                                 uint32_t* __restrict__ cur, uint32_t* __restrict__ pf) {
   const uint32_t tot = wave_scan_nb([&](uint32_t b) { return cnt[b]; },
                                     [&](uint32_t b, uint32_t e) {
                                       off[b] = e;
                                       cur[b] = e;
                                     });
   if (threadIdx.x == 0) off[MSM_NB] = tot;
-  for (uint32_t lv = 0; lv < nlev; ++lv) {
-    // level 0: every even entry (its pair, or alone at a bucket's odd end); level l: entries
-    // k = j 2^(l+1) whose partner k + 2^l exists
-    const uint32_t h = 1u << lv;
-    uint32_t* p = pf + (size_t)lv * (MSM_NB + 1);
+  for (uint32_t row = 0; row < MSM_PF_ROWS; ++row) {
+    // row 0: level-0 pairs, every even entry (its pair, or alone at a bucket's odd end);
+    // row 1: chunks of MSM_CH entries
+    uint32_t* p = pf + (size_t)row * (MSM_NB + 1);
     const uint32_t t = wave_scan_nb(
         [&](uint32_t b) {
           const uint32_t c = cnt[b];
-          return lv == 0 ? (c + 1) / 2 : (c > h ? (c - h + 2 * h - 1) >> (lv + 1) : 0u);
+          return row == 0 ? (c + 1) / 2 : (c + MSM_CH - 1) >> MSM_CH_LV;
         },
         [&](uint32_t b, uint32_t e) { p[b] = e; });
     if (threadIdx.x == 0) p[MSM_NB] = t;
@@ -151,7 +157,6 @@ __global__ __launch_bounds__(64) void k_sig_as_S(Slab st, const int32_t* __restr
   U.st(v, c, 0);
 }
 
-enum : uint32_t { MSM_L0 = 0, MSM_LVL = 1, MSM_T0 = 2, MSM_TL = 3, MSM_HRN = 4 };
 // operand source: identity, a vote's sigma / tau (affine, staged with Z = 1), A or U entry
 enum : uint32_t { SRC_ID = 0, SRC_PT = 1, SRC_A = 2, SRC_U = 3 };
 
@@ -188,63 +193,16 @@ __device__ __forceinline__ void msm_coord(Fp& v, const MsmArgs& a, uint32_t kind
   }
 }
 
-// One pair add per W-lane slice: dst = A + B (madd / padd) or A + [2^m] B (hdbl<m>).
-// lv: the tree level (MSM_LVL, MSM_TL) or the combination level h = 1..5 (MSM_HRN).
-template <int W, int MODE>
-__global__ __launch_bounds__(64) void k_msm_pair(uint32_t lv, VmDev prog, uint32_t nin, uint32_t stride_w,
-                                                 const uint32_t* __restrict__ cst_g, MsmArgs a) {
-  constexpr uint32_t SL = 64 / W;
-  const uint32_t* row = a.pf + (size_t)(MODE == MSM_L0 ? 0 : lv) * (MSM_NB + 1);
-  const uint32_t total = MODE == MSM_L0 || MODE == MSM_LVL ? row[MSM_NB]
-                         : MODE == MSM_T0                  ? MSM_U
-                         : MODE == MSM_TL                  ? MSM_NT * (MSM_TM >> lv)
-                                                           : (MSM_NT >> lv);
-  if (blockIdx.x * SL >= total) return;  // whole workgroup idle (empty upper tree levels)
-  // above the pool's waves (2), as k_vm_final: the MSM levels are the final stream's longest
-  // stretch beside the pool (r05y pool log: 1.7-2.9 ms against 0.67 alone). r05q: at 2 (with the
-  // final at 3) 1,432k verifs/s vs 1,131k-1,316k at 0; r05z: at 3, 1,389k-1,407k vs 1,378k-1,386k
-  __builtin_amdgcn_s_setprio(3);
-  extern __shared__ uint4 lds4[];
-  uint32_t* lds = reinterpret_cast<uint32_t*>(lds4);
-  uint32_t* cst = lds;
-  const uint32_t slice = threadIdx.x / W, lane = threadIdx.x % W;
-  uint32_t* slots = lds + SLOT_BASE_W + slice * stride_w;
-  const uint32_t q = blockIdx.x * SL + slice;
-  const bool active = q < total;
-  load_consts(cst, cst_g, VM_NCONST);
-  uint32_t ka = SRC_ID, ia = 0, kb = SRC_ID, ib = 0, kd = SRC_A, id = 0;
+// One pair add on the calling thread's W-lane slice: dst = A + B (madd / padd) or A + [2^m] B
+// (hdbl<m>). Every thread of the workgroup calls it (the barriers); `active` marks the slices
+// with a pair. The caller has loaded the constants; results go to global memory (canonical),
+// and the closing __syncthreads() makes them the next level's operands within the workgroup
+// (and keeps the next pair's staging behind this one's reads of the slots).
+template <int W>
+__device__ __forceinline__ void msm_pair_op(const VmDev& prog, uint32_t nin, uint32_t* slots, const uint32_t* cst,
+                                            uint32_t lane, bool active, const MsmArgs& a, uint32_t ka, uint32_t ia,
+                                            uint32_t kb, uint32_t ib, uint32_t kd, uint32_t id) {
   if (active) {
-    if (MODE == MSM_L0 || MODE == MSM_LVL) {
-      const uint32_t b = msm_find(row, q), j = q - row[b];
-      const uint32_t a0 = a.pf[b];  // A index of the bucket's entry 0
-      if (MODE == MSM_L0) {
-        const uint32_t k = 2 * j, e = a.off[b] + k;
-        ka = SRC_PT, ia = a.ent[e];
-        if (k + 1 < a.cnt[b]) kb = SRC_PT, ib = a.ent[e + 1];
-        id = a0 + j;
-      } else {
-        const uint32_t k = j << (lv + 1);
-        ka = SRC_A, ia = a0 + (k >> 1);
-        kb = SRC_A, ib = a0 + ((k + (1u << lv)) >> 1);
-        id = ia;
-      }
-    } else if (MODE == MSM_T0) {
-      const uint32_t t = q / MSM_TM, i = q % MSM_TM, w = t >> 3, k = t & 7;
-      const uint32_t b0 = w * MSM_NBW + msm_member(2 * i, k) - 1, b1 = w * MSM_NBW + msm_member(2 * i + 1, k) - 1;
-      if (a.cnt[b0]) ka = SRC_A, ia = a.pf[b0];
-      if (a.cnt[b1]) kb = SRC_A, ib = a.pf[b1];
-      kd = SRC_U, id = q;
-    } else if (MODE == MSM_TL) {
-      const uint32_t per = MSM_TM >> lv, t = q / per, i = q % per, e = t * MSM_TM + (i << lv);
-      ka = SRC_U, ia = e;
-      kb = SRC_U, ib = e + (1u << (lv - 1));
-      kd = SRC_U, id = e;
-    } else {  // window combination level h = lv: U[2 m i] + [2^m] U[2 m i + m] (targets), m = 2^(h-1)
-      const uint32_t m = 1u << (lv - 1), e = 2 * m * q * MSM_TM;
-      ka = SRC_U, ia = e;
-      kb = SRC_U, ib = e + m * MSM_TM;
-      kd = SRC_U, id = e;
-    }
     // stage the operands: madd takes A affine (4 inputs) then B; the others A, B projective
     const uint32_t na = nin - 6;
     for (uint32_t k = lane; k < nin; k += W) {
@@ -264,6 +222,138 @@ __global__ __launch_bounds__(64) void k_msm_pair(uint32_t lv, VmDev prog, uint32
       for (int l = 0; l < 12; ++l) v.v[l] = slots[src * 12 + l];
       vm::canon(v, v);
       d.st(v, k, id);
+    }
+  }
+  __syncthreads();
+}
+
+// the program of a level, picked field by field (kernel arguments stay in scalar registers)
+__device__ __forceinline__ VmDev msm_prog(bool first, const VmDev& x, const VmDev& y) {
+  VmDev r;
+  r.code = first ? x.code : y.code;
+  r.nphases = first ? x.nphases : y.nphases;
+  r.in = first ? x.in : y.in;
+  r.out = first ? x.out : y.out;
+  r.trace = nullptr, r.clk = nullptr, r.side = nullptr;
+  return r;
+}
+
+// The MSM's VM kernels are one-wave workgroups that own every entry they touch, so the levels
+// of a tree run inside one launch: a level's results are written to the workgroup's own global
+// lines, a __syncthreads() orders them before the next level's loads (one CU, one L1), and no
+// workgroup ever waits for another. All of them run above the pool's waves (s_setprio 3 against
+// 2, as k_vm_final): the MSM is the final stream's longest stretch beside the pool (r05y pool
+// log: 1.7-2.9 ms against 0.67 alone). r05q: at 2 (with the final at 3) 1,432k verifs/s vs
+// 1,131k-1,316k at 0; r05z: at 3, 1,389k-1,407k vs 1,378k-1,386k.
+#define MSM_VM_PROLOGUE(W)                                    \
+  __builtin_amdgcn_s_setprio(3);                              \
+  extern __shared__ uint4 lds4[];                             \
+  uint32_t* lds = reinterpret_cast<uint32_t*>(lds4);          \
+  const uint32_t* cst = lds;                                  \
+  const uint32_t slice = threadIdx.x / (W), lane = threadIdx.x % (W); \
+  uint32_t* slots = lds + SLOT_BASE_W + slice * stride_w;     \
+  load_consts(lds, cst_g, VM_NCONST)
+
+// Bucket trees, levels 0 .. MSM_CH_LV - 1: workgroup g owns chunk j of bucket b (pfc[b] <= g <
+// pfc[b + 1], j = g - pfc[b]), the bucket's entries 64 j .. 64 j + 63. Level 0 adds the points
+// of an even entry and its successor (madd; alone at the bucket's odd end) into A, level l
+// adds entry k + 2^l into entry k = j' 2^(l+1) (padd, in place): every pair of these levels
+// lies inside one aligned chunk of 2^MSM_CH_LV entries. Eight pairs per run of the wave.
+__global__ __launch_bounds__(64) void k_msm_chunk(VmDev madd, VmDev padd, uint32_t stride_w,
+                                                  const uint32_t* __restrict__ cst_g, MsmArgs a) {
+  constexpr uint32_t W = VM_MADD_W, SL = 64 / W;
+  const uint32_t* rowc = a.pf + (MSM_NB + 1);
+  if (blockIdx.x >= rowc[MSM_NB]) return;  // the grid is the worst case's
+  MSM_VM_PROLOGUE(W);
+  const uint32_t b = msm_find(rowc, blockIdx.x), k0 = (blockIdx.x - rowc[b]) << MSM_CH_LV;
+  const uint32_t c = a.cnt[b], a0 = a.pf[b], e0 = a.off[b];
+  const uint32_t m = c - k0 < MSM_CH ? c - k0 : MSM_CH;  // the chunk's entries (>= 1)
+  for (uint32_t lv = 0; lv < MSM_CH_LV && (lv == 0 || (1u << lv) < m); ++lv) {
+    const uint32_t h = 1u << lv;
+    const uint32_t np = lv == 0 ? (m + 1) / 2 : (m - h + 2 * h - 1) >> (lv + 1);
+    const VmDev prog = msm_prog(lv == 0, madd, padd);
+    for (uint32_t r = 0; r < np; r += SL) {
+      const uint32_t p = r + slice, k = k0 + (p << (lv + 1));
+      const bool act = p < np;
+      uint32_t ka = SRC_A, ia = a0 + (k >> 1), kb = SRC_A, ib = a0 + ((k + h) >> 1);
+      const uint32_t id = ia;
+      if (lv == 0) {
+        ka = SRC_PT, kb = SRC_ID, ia = ib = 0;
+        if (act) {
+          ia = a.ent[e0 + k];
+          if (k + 1 < c) kb = SRC_PT, ib = a.ent[e0 + k + 1];
+        }
+      }
+      msm_pair_op<W>(prog, lv == 0 ? VM_MADD_NIN : VM_PADD_NIN, slots, cst, lane, act, a, ka, ia, kb, ib, SRC_A, id);
+    }
+  }
+}
+
+// Bucket trees, levels >= MSM_CH_LV: workgroup b owns bucket b and adds its chunks' sums
+// (entries 64 j) level by level; a bucket of one chunk (every bucket of a batch whose RLC
+// digits spread evenly, up to ~6,000 votes) exits at once, so a level without live pairs costs
+// nothing anywhere.
+__global__ __launch_bounds__(64) void k_msm_upper(VmDev padd, uint32_t stride_w, const uint32_t* __restrict__ cst_g,
+                                                  MsmArgs a) {
+  constexpr uint32_t W = VM_PADD_W, SL = 64 / W;
+  const uint32_t c = a.cnt[blockIdx.x];
+  if (c <= MSM_CH) return;
+  MSM_VM_PROLOGUE(W);
+  const uint32_t a0 = a.pf[blockIdx.x];
+  for (uint32_t lv = MSM_CH_LV; (1u << lv) < c; ++lv) {
+    const uint32_t h = 1u << lv, np = (c - h + 2 * h - 1) >> (lv + 1);
+    for (uint32_t r = 0; r < np; r += SL) {
+      const uint32_t p = r + slice, k = p << (lv + 1);
+      const uint32_t ia = a0 + (k >> 1), ib = a0 + ((k + h) >> 1);
+      msm_pair_op<W>(padd, VM_PADD_NIN, slots, cst, lane, p < np, a, SRC_A, ia, SRC_A, ib, SRC_A, ia);
+    }
+  }
+}
+
+// Bit-plane sums, levels lo .. hi of the 32 fixed 128-leaf trees (level 0: pairs of member
+// buckets into U; level l: U[e] += U[e + 2^(l-1)], e = t TM + (i << l)): workgroup g owns the
+// 2^hi level-0 pairs g 2^hi .. of target t = g / (TM >> hi), i.e. the (G >> l) pairs
+// i = (g % (TM >> hi)) (G >> l) + p of level l. Two launches (0 .. 3 on 256 workgroups, 4 .. 6
+// on 32) are seven runs deep; one workgroup per tree would be eighteen.
+__global__ __launch_bounds__(64) void k_msm_plane(uint32_t lo, uint32_t hi, VmDev padd, uint32_t stride_w,
+                                                  const uint32_t* __restrict__ cst_g, MsmArgs a) {
+  constexpr uint32_t W = VM_PADD_W, SL = 64 / W;
+  MSM_VM_PROLOGUE(W);
+  const uint32_t per_t = MSM_TM >> hi, t = blockIdx.x / per_t, g = blockIdx.x % per_t;
+  for (uint32_t lv = lo; lv <= hi; ++lv) {
+    const uint32_t np = 1u << (hi - lv);
+    for (uint32_t r = 0; r < np; r += SL) {
+      const uint32_t p = r + slice, i = g * np + p;
+      const bool act = p < np;
+      uint32_t ka = SRC_U, ia = t * MSM_TM + (i << lv), kb = SRC_U, ib = ia + (lv ? 1u << (lv - 1) : 0u);
+      const uint32_t id = ia;
+      if (lv == 0) {
+        ka = kb = SRC_ID, ia = ib = 0;
+        if (act) {
+          const uint32_t w = t >> 3, k = t & 7;
+          const uint32_t b0 = w * MSM_NBW + msm_member(2 * i, k) - 1, b1 = w * MSM_NBW + msm_member(2 * i + 1, k) - 1;
+          if (a.cnt[b0]) ka = SRC_A, ia = a.pf[b0];
+          if (a.cnt[b1]) kb = SRC_A, ib = a.pf[b1];
+        }
+      }
+      msm_pair_op<W>(padd, VM_PADD_NIN, slots, cst, lane, act, a, ka, ia, kb, ib, SRC_U, id);
+    }
+  }
+}
+
+// Window combination sum_t 2^t T_t, levels lo .. hi (<= lo + 2) of U[2 m q TM] += [2^m] U[(2 m q
+// + m) TM], m = 2^(h-1) (programs hdbl<m>: p0 is level lo's): workgroup g owns the targets
+// g 2^hi .., i.e. the 2^(hi-h) pairs q = g 2^(hi-h) + p of level h.
+__global__ __launch_bounds__(64) void k_msm_comb(uint32_t lo, uint32_t hi, VmDev p0, VmDev p1, VmDev p2,
+                                                 uint32_t stride_w, const uint32_t* __restrict__ cst_g, MsmArgs a) {
+  constexpr uint32_t W = VM_HDBL1_W, SL = 64 / W;
+  MSM_VM_PROLOGUE(W);
+  for (uint32_t h = lo; h <= hi; ++h) {
+    const VmDev prog = msm_prog(h == lo, p0, msm_prog(h == lo + 1, p1, p2));
+    const uint32_t np = 1u << (hi - h), m = 1u << (h - 1);
+    for (uint32_t r = 0; r < np; r += SL) {
+      const uint32_t p = r + slice, e = 2 * m * (blockIdx.x * np + p) * MSM_TM;
+      msm_pair_op<W>(prog, VM_HDBL1_NIN, slots, cst, lane, p < np, a, SRC_U, e, SRC_U, e + m * MSM_TM, SRC_U, e);
     }
   }
 }

@@ -2881,7 +2881,7 @@ static int sync_all(ovh_ctx* c) {
 static size_t msm_acap(uint32_t cap) { return (size_t)4 * cap + MSM_NB; }
 static size_t msm_round(size_t w) { return (w + 63) / 64 * 64; }
 static size_t msm_words(uint32_t cap) {
-  return msm_round(MSM_NB) + msm_round(MSM_NB + 1) + msm_round(MSM_NB) + msm_round((size_t)MSM_LV * (MSM_NB + 1)) +
+  return msm_round(MSM_NB) + msm_round(MSM_NB + 1) + msm_round(MSM_NB) + msm_round((size_t)MSM_PF_ROWS * (MSM_NB + 1)) +
          msm_round((size_t)8 * cap) + msm_round((size_t)6 * 12 * msm_acap(cap)) + (size_t)6 * 12 * MSM_U;
 }
 static MsmArgs msm_args(ovh_ctx* c, int slot, uint32_t** cur) {
@@ -2894,7 +2894,7 @@ static MsmArgs msm_args(ovh_ctx* c, int slot, uint32_t** cur) {
   *cur = p;
   p += msm_round(MSM_NB);
   a.pf = p;
-  p += msm_round((size_t)MSM_LV * (MSM_NB + 1));
+  p += msm_round((size_t)MSM_PF_ROWS * (MSM_NB + 1));
   a.ent = p;
   p += msm_round((size_t)8 * c->cap);
   a.A = Slab{p, (uint32_t)msm_acap(c->cap)};
@@ -3234,32 +3234,26 @@ static int enqueue_msm(ovh_ctx* c, hipStream_t st, int slot, uint32_t n, const i
     k_sig_as_S<<<1, 64, 0, st>>>(a.st, d_codes, a.U);
     return hipGetLastError() == hipSuccess ? 0 : OVH_ERR_DEVICE;
   }
-  uint32_t nlev = 1;  // tree levels: 2^nlev >= the largest possible bucket (2n points)
-  while ((1ull << nlev) < 2ull * n) ++nlev;
-  if (nlev > MSM_LV) return OVH_ERR_ARG;
+  if (2ull * n > (1ull << MSM_LV)) return OVH_ERR_ARG;  // a bucket holds up to 2n points: MSM_LV tree levels
   k_msm_zero<<<(MSM_NB + MSM_TPB - 1) / MSM_TPB, MSM_TPB, 0, st>>>((uint32_t*)a.cnt);  // (one-wave workgroups)
   const uint32_t nb = (n + MSM_TPB - 1) / MSM_TPB;
   k_msm_count<<<nb, MSM_TPB, 0, st>>>(n, seed, base, d_codes, (uint32_t*)a.cnt);
-  k_msm_scan<<<1, 64, 0, st>>>(nlev, a.cnt, (uint32_t*)a.off, cur, (uint32_t*)a.pf);
+  k_msm_scan<<<1, 64, 0, st>>>(a.cnt, (uint32_t*)a.off, cur, (uint32_t*)a.pf);
   k_msm_scatter<<<nb, MSM_TPB, 0, st>>>(n, seed, base, d_codes, cur, (uint32_t*)a.ent);
-  constexpr uint32_t SL8 = 64 / VM_MADD_W, SL16 = 64 / VM_HDBL1_W;
-  auto grid = [](uint64_t pairs, uint32_t sl) { return (uint32_t)((pairs + sl - 1) / sl); };
-  // bucket trees: level 0 pairs (<= 4n + NB), level l (<= 8n / 2^(l+1) + NB), in place
-  k_msm_pair<VM_MADD_W, MSM_L0><<<grid(4ull * n + MSM_NB, SL8), 64, LDS_MSM8, st>>>(0, c->vm_madd, VM_MADD_NIN,
-                                                                                     MSM8_STRIDE_W, c->vm_consts, a);
-  for (uint32_t lv = 1; lv < nlev; ++lv)
-    k_msm_pair<VM_PADD_W, MSM_LVL><<<grid((8ull * n >> (lv + 1)) + MSM_NB, SL8), 64, LDS_MSM8, st>>>(
-        lv, c->vm_padd, VM_PADD_NIN, MSM8_STRIDE_W, c->vm_consts, a);
-  // bit-plane sums T_t (128 buckets each): pairs of buckets, then 6 levels
-  k_msm_pair<VM_PADD_W, MSM_T0><<<grid(MSM_U, SL8), 64, LDS_MSM8, st>>>(0, c->vm_padd, VM_PADD_NIN, MSM8_STRIDE_W,
-                                                                        c->vm_consts, a);
-  for (uint32_t lv = 1; lv <= 6; ++lv)
-    k_msm_pair<VM_PADD_W, MSM_TL><<<grid(MSM_NT * (MSM_TM >> lv), SL8), 64, LDS_MSM8, st>>>(
-        lv, c->vm_padd, VM_PADD_NIN, MSM8_STRIDE_W, c->vm_consts, a);
-  // sum_t 2^t T_t: five levels of A + [2^m] B, m = 1, 2, 4, 8, 16
-  for (uint32_t h = 1; h <= 5; ++h)
-    k_msm_pair<VM_HDBL1_W, MSM_HRN><<<grid(MSM_NT >> h, SL16), 64, LDS_HDBL, st>>>(
-        h, c->vm_hdbl[h - 1], VM_HDBL1_NIN, HDBL_STRIDE_W, c->vm_consts, a);
+  // Every VM kernel below runs several tree levels inside one-wave workgroups that own what they
+  // touch (msm.hpp): six launches where each level used to be one (25 at 4,096 votes).
+  // bucket trees: levels 0-5 per 64-entry chunk of a bucket (<= 8n / 64 + NB chunks), then the
+  // levels above per bucket (no bucket has them up to 32 votes)
+  k_msm_chunk<<<(uint32_t)((8ull * n >> MSM_CH_LV) + MSM_NB), 64, LDS_MSM8, st>>>(c->vm_madd, c->vm_padd, MSM8_STRIDE_W,
+                                                                                   c->vm_consts, a);
+  if (2ull * n > MSM_CH) k_msm_upper<<<MSM_NB, 64, LDS_MSM8, st>>>(c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
+  // bit-plane sums T_t (128 buckets each): levels 0-3 per 16 buckets, then 4-6 per target
+  k_msm_plane<<<MSM_NT * (MSM_TM >> 3), 64, LDS_MSM8, st>>>(0, 3, c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
+  k_msm_plane<<<MSM_NT, 64, LDS_MSM8, st>>>(4, 6, c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
+  // sum_t 2^t T_t: five levels of A + [2^m] B, m = 1, 2, 4 (per 8 targets), then 8, 16
+  k_msm_comb<<<MSM_NT >> 3, 64, LDS_HDBL, st>>>(1, 3, c->vm_hdbl[0], c->vm_hdbl[1], c->vm_hdbl[2], HDBL_STRIDE_W,
+                                                c->vm_consts, a);
+  k_msm_comb<<<1, 64, LDS_HDBL, st>>>(4, 5, c->vm_hdbl[3], c->vm_hdbl[4], c->vm_hdbl[4], HDBL_STRIDE_W, c->vm_consts, a);
   return hipGetLastError() == hipSuccess ? 0 : OVH_ERR_DEVICE;
 }
 
@@ -4276,8 +4270,12 @@ ovh_ctx* ovh_create(int device, const uint8_t* dst, size_t dst_len, uint32_t fla
   }
   int lo = 0, hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&lo, &hi);  // lo = numerically largest = lowest priority
-  // streams: ovh_stream (normal priority), three final streams (lowest), the two pool streams
-  // (highest; created with the context, so each holds a hardware queue of its own)
+  // streams: ovh_stream (normal priority), the NFIN_STREAMS = 4 final streams (lowest; OVH_NFIN
+  // 2 or 3 creates three), the two pool streams (highest; a third with three shard streams).
+  // The runtime keeps a set of hardware queues per priority (GPU_MAX_HW_QUEUES each, four by
+  // default): the four final streams fill the low-priority set one queue each, the pool streams
+  // draw from the high-priority set and ovh_stream from the normal one. A fifth stream of one
+  // priority shares a queue and runs in order behind another.
   bool ok = xmd_build_templates(c->xmd, dst, (uint32_t)dst_len) &&
             stream_new(&c->stream, 0) == hipSuccess &&
             stream_new(&c->fstream, lo) == hipSuccess &&
@@ -4846,8 +4844,10 @@ int ovh_aggregate_sigs(ovh_ctx* c, const uint8_t* sigs, const size_t* sig_lens, 
   if (n) {
     // the keys parse on the side stream while the signatures run through the VM
     HIPCHK(hipEventRecord(c->ev_x[2], c->stream));  // staged inputs
-    // created on first use: a context that only verifies batches keeps to three streams, which
-    // map onto distinct hardware queues at HIP's default of four (GPU_MAX_HW_QUEUES)
+    // created on first use: a context that only verifies batches keeps to the streams of
+    // ovh_create (ovh_stream, four final, two pool: at most four per priority, so each has a
+    // hardware queue of its own at HIP's default of four per priority, GPU_MAX_HW_QUEUES). This
+    // one is the normal-priority set's second stream, beside ovh_stream.
     if (!c->xstream) HIPCHK(stream_new(&c->xstream, 0));
     HIPCHK(hipStreamWaitEvent(c->xstream, c->ev_x[2], 0));
     bool keys48 = true;
