@@ -309,6 +309,49 @@ class ConsensusCrypto:
                                                codes.ctypes.data_as(ctypes.c_void_p)))
         return codes[:n]
 
+    def build_qc_raw(self, signatures, hash_, voters):
+        """ovh_build_qc without raising on "no vote taken": (code, aggregated_signature or None,
+        bitmap, codes int32[n], taken bool[n], n_signed). code is 0 or 4; anything else raises."""
+        n = len(signatures)
+        if len(voters) != n:
+            raise Other("signatures length does not match voters length")
+        sig = b"".join(bytes(s) for s in signatures)
+        pk = b"".join(bytes(v) for v in voters)
+        if len(sig) != 96 * n or len(pk) != 48 * n:
+            raise ValueError("build_qc takes 96-byte signatures and 48-byte voters")
+        h = bytes(hash_)
+        codes = np.zeros(max(n, 1), dtype=np.int32)
+        taken = np.zeros(max(n, 1), dtype=np.uint8)
+        bl = (len(self.pubkeys) + 7) // 8
+        bitmap = ctypes.create_string_buffer(max(bl, 1))
+        out = ctypes.create_string_buffer(96)
+        cnt = ctypes.c_uint32(0)
+        code = self.lib.ovh_build_qc(self.ctx.ptr, n, sig, h, len(h), pk, codes.ctypes.data_as(ctypes.c_void_p),
+                                     taken.ctypes.data_as(ctypes.c_void_p), out, bitmap, bl, ctypes.byref(cnt))
+        if code not in (OK, 4):
+            raise_for(code)
+        return code, (out.raw if code == OK else None), bitmap.raw[:bl], codes[:n], taken[:n].astype(bool), int(cnt.value)
+
+    def build_qc(self, signatures, hash_, voters):
+        """The leader's side of a round in one device pass (ovh_build_qc): verify the round's
+        votes on `hash_`, take per validator (update_pubkeys) its first valid vote, aggregate the
+        taken signatures. Returns (aggregated_signature, bitmap, codes, taken): the bitmap is MSB
+        first over the key-sorted validator list (extract_voters / verify_qc_batch order), codes[i]
+        the verify_signature result of vote i (also entered in the verdict cache), taken bool[n].
+        Raises CryptoErr(4) when no vote is taken, as aggregate_signatures of an empty list."""
+        code, agg, bitmap, codes, taken, _ = self.build_qc_raw(signatures, hash_, voters)
+        raise_for(code)
+        return agg, bitmap, codes, taken
+
+    def build_proof(self, height: int, round_: int, block_hash: bytes, signatures, voters) -> bytes:
+        """The overlord Proof of a block from the round's precommits: the vote hash
+        hash(rlp(Vote{height, round, Precommit, block_hash})), build_qc over it, and the Proof's
+        RLP bytes (vote.encode_proof), which check_block accepts."""
+        from . import vote as _vote
+        vh = _vote.vote_hash(self, height, round_, _vote.PRECOMMIT, block_hash)
+        agg, bitmap, _, _ = self.build_qc(signatures, vh, voters)
+        return _vote.encode_proof(height, round_, block_hash, agg, bitmap)
+
     # ---- Consensus::check_block (consensus.rs:143-207) over the Crypto surface ----
     def check_block(self, proposal_height: int, proposal_data: bytes, proof: bytes,
                     authority_list: Optional[Sequence[bytes]] = None) -> bool:

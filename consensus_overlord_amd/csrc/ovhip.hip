@@ -1966,6 +1966,7 @@ __global__ __launch_bounds__(64) void k_vm_signg(uint32_t n, VmDev p0, VmDev p1,
 }
 
 #include "msm.hpp"
+#include "qc.hpp"
 
 // Validator table (ovh_set_validators) and the keys of verify_aggregated_signature: one 48-byte
 // compressed key per 16-lane slice (program "pkchk": decompression + G1 subgroup check) -> flags
@@ -2371,6 +2372,8 @@ struct ValidatorTable {
   uint32_t n = 0, cap = 0;
   uint32_t* planes = nullptr;   // X, Y, Z planes of `cap` entries
   uint32_t* flags = nullptr;    // device PKF_* per entry
+  // ovh_build_qc: owner (cap) | entry -> sorted rank (cap) | bitmap words (cap / 32) | count
+  uint32_t* qc = nullptr;
   std::vector<uint32_t> hflags;  // host copy
   std::vector<std::string> keys;
   std::unordered_map<std::string, uint32_t> index;  // key bytes -> first entry
@@ -4397,7 +4400,7 @@ static void destroy_one(ovh_ctx* c) {
   for (void* p : {(void*)c->in_buf, (void*)c->part_out, (void*)c->result, (void*)c->pool_q, (void*)c->pool_desc,
                   (void*)c->pool_scr, (void*)c->plog, (void*)c->vm_consts,
                   (void*)c->fin, (void*)c->scr, (void*)c->scr_pk, (void*)c->scr_sig, (void*)c->comb,
-                  (void*)c->tab.planes, (void*)c->tab.flags, (void*)c->qc_buf, (void*)c->qt_buf, (void*)c->hc_planes, (void*)c->hc_inf, (void*)c->gather,
+                  (void*)c->tab.planes, (void*)c->tab.flags, (void*)c->tab.qc, (void*)c->qc_buf, (void*)c->qt_buf, (void*)c->hc_planes, (void*)c->hc_inf, (void*)c->gather,
                   (void*)c->mfin, (void*)c->sm1_plan, (void*)c->sm1_hash})
     if (p) (void)hipFree(p);
   for (void* p : c->vm_bufs) (void)hipFree(p);
@@ -5165,13 +5168,15 @@ static int set_validators_locked(ovh_ctx* c, const uint8_t* pks, size_t n) {
   uint32_t cap = 64;
   while (cap < n) cap <<= 1;
   if (cap > t.cap || !t.planes) {
-    for (void* p : {(void*)t.planes, (void*)t.flags})
+    for (void* p : {(void*)t.planes, (void*)t.flags, (void*)t.qc})
       if (p) (void)hipFree(p);
     t.planes = nullptr;
     t.flags = nullptr;
+    t.qc = nullptr;
     t.cap = 0;
     HIPCHK(hipMalloc(&t.planes, (size_t)3 * 12 * cap * 4));
     HIPCHK(hipMalloc(&t.flags, (size_t)cap * 4));
+    HIPCHK(hipMalloc(&t.qc, ((size_t)2 * cap + cap / 32 + 1) * 4));
     t.cap = cap;
   }
   t.n = 0;
@@ -5195,6 +5200,13 @@ static int set_validators_locked(ovh_ctx* c, const uint8_t* pks, size_t n) {
     t.sorted.push_back((uint32_t)i);
   }
   std::stable_sort(t.sorted.begin(), t.sorted.end(), [&](uint32_t a, uint32_t b) { return t.keys[a] < t.keys[b]; });
+  if (n) {  // entry -> sorted rank, for ovh_build_qc's bitmap (a table lookup gives a key's first entry,
+            // which the stable sort puts first among equal keys)
+    std::vector<uint32_t> rank(n);
+    for (size_t k = 0; k < n; ++k) rank[t.sorted[k]] = (uint32_t)k;
+    HIPCHK(hipMemcpyAsync(t.qc + t.cap, rank.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
   t.n = (uint32_t)n;
   return 0;
 }
@@ -5365,6 +5377,152 @@ int ovh_verify_qc_batch(ovh_ctx* c, size_t nq, const uint8_t* sigs, const uint8_
   std::lock_guard<std::mutex> g(s->mu);
   if (!s->tab.n) return OVH_ERR_ARG;
   return qc_batch_locked(s, nq, sigs, hashes, bitmaps, bitmap_len, codes);
+}
+
+// ovh_build_qc on one device (caller holds c->mu, the table is set): the round's verify batch on
+// the same-message path (every vote signs `hash`; its vote program leaves each sigma, affine and
+// subgroup-checked, in the slot's state slab), then on the batch's final stream, behind the
+// bisection: the selection (qc.hpp), the masked G2 sum of the taken sigma and its compression.
+// One vote: the per-call check (verify_one_locked keeps no sigma), then sigma from one sigchk
+// launch without the subgroup check. One host synchronisation, after everything is enqueued; the
+// host staging lives until then.
+static int build_qc_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* hashes, const uint8_t* pks,
+                           int32_t* codes, uint8_t* taken, uint8_t* out_sig, uint8_t* bitmap, size_t bitmap_len,
+                           uint32_t* n_signed) {
+  HIPCHK(hipSetDevice(c->device));
+  const ValidatorTable& tb = c->tab;
+  const uint32_t N = (uint32_t)n;
+  std::vector<uint32_t> perm;
+  std::vector<int32_t> tidx;
+  const size_t t = table_split(c, n, pks, perm, tidx);
+  SameMsgPlan pl;
+  if (n >= 2) samemsg_plan(n, hashes, perm, pl);
+  // staging: sigs | (hashes) | pks | codes | table indices, the plan, then orig | taken | a zero
+  // offset and a code word (sigchk) | the 96 output bytes
+  pl.off = (n * (96 + 32 + 48 + 4 + 4) + 255) / 256 * 256;
+  const size_t qoff = (pl.off + pl.bytes + 255) / 256 * 256;
+  const size_t zoff = qoff + 8 * n, ooff = zoff + 16;
+  CHK(ensure_in(c, ooff + 96));
+  CHK(ensure_cap(c, n));
+  uint8_t* d = c->in_buf;
+  int32_t* dc = (int32_t*)(d + n * 176);
+  const int32_t* dtidx = (const int32_t*)(d + n * 180);
+  uint32_t* dorig = (uint32_t*)(d + qoff);
+  uint32_t* dtaken = dorig + n;
+  std::vector<uint8_t> hb, hp;
+  std::vector<int32_t> pc(n);
+  std::vector<uint32_t> ptk(n);
+  uint32_t cnt = 0;
+  uint8_t sig96[96];
+  // an error return drains the streams that copy from / into the host buffers above before they
+  // die; the normal return has waited already (the call's one synchronisation)
+  struct Drain {
+    hipStream_t s[2];
+    bool armed;
+    ~Drain() {
+      if (armed)
+        for (hipStream_t x : s)
+          if (x) (void)hipStreamSynchronize(x);
+    }
+  } drain{{c->stream, nullptr}, true};
+  if (perm.empty()) {
+    HIPCHK(hipMemcpyAsync(d, sigs, n * 96, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d + n * 128, pks, n * 48, hipMemcpyHostToDevice, c->stream));
+  } else {
+    hb.resize(n * 144);
+    for (size_t j = 0; j < n; ++j) {
+      memcpy(&hb[96 * j], sigs + 96 * (size_t)perm[j], 96);
+      memcpy(&hb[n * 96 + 48 * j], pks + 48 * (size_t)perm[j], 48);
+    }
+    HIPCHK(hipMemcpyAsync(d, hb.data(), n * 96, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d + n * 128, hb.data() + n * 96, n * 48, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dorig, perm.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+  }
+  if (t) HIPCHK(hipMemcpyAsync(d + n * 180, tidx.data(), t * 4, hipMemcpyHostToDevice, c->stream));
+  int slot;
+  hipStream_t st;
+  if (n == 1) {
+    HIPCHK(hipMemsetAsync(d + zoff, 0, 16, c->stream));  // sigchk's offset word
+    HIPCHK(hipMemcpyAsync(d + 96, hashes, 32, hipMemcpyHostToDevice, c->stream));
+    CHK(verify_one_locked(c, d, d + 96, staged_key(c, n, d, t, 0), dc, hashes));
+    slot = c->last_slot;
+    st = c->stream;
+  } else {
+    hp.resize(pl.bytes);
+    memcpy(hp.data(), pl.gid.data(), 4 * n);
+    memcpy(hp.data() + 4 * n, pl.ghash.data(), 32 * (size_t)pl.G);
+    memcpy(hp.data() + 4 * n + 32 * (size_t)pl.G, pl.head.data(), 4 * (size_t)pl.G);
+    if (!pl.pairs.empty()) memcpy(hp.data() + 4 * n + 36 * (size_t)pl.G, pl.pairs.data(), 4 * pl.pairs.size());
+    HIPCHK(hipMemcpyAsync(d + pl.off, hp.data(), pl.bytes, hipMemcpyHostToDevice, c->stream));
+    const uint8_t* ex = d + pl.off;
+    const uint32_t* head = (const uint32_t*)(ex + 4 * n + 32 * (size_t)pl.G);
+    const SameMsgDev pd{pl.G, (const uint32_t*)ex, ex + 4 * n, head, head + pl.G, &pl.level_off};
+    CHK(take_slot(c, &slot));
+    CHK(verify_samemsg_locked(c, slot, n, d, t, dtidx, d + n * 128 + 48 * t, pd, dc));
+    st = c->fs[slot];
+  }
+  uint32_t* cur;
+  const MsmArgs a = msm_args(c, slot, &cur);  // the MSM's bucket trees are done with: A holds the sum's tree
+  QcSel sel;
+  sel.codes = dc;
+  sel.tidx = dtidx;
+  sel.orig = perm.empty() ? nullptr : dorig;
+  sel.owner = tb.qc;
+  sel.rank = tb.qc + tb.cap;
+  sel.bitmap = tb.qc + 2 * (size_t)tb.cap;
+  sel.count = sel.bitmap + tb.cap / 32;
+  sel.taken = dtaken;
+  k_qc_reset<<<nblk(tb.n), WG, 0, st>>>(tb.n, sel);
+  if (t) k_qc_claim<<<nblk(t), WG, 0, st>>>((uint32_t)t, sel);
+  k_qc_mark<<<nblk(n), WG, 0, st>>>(N, (uint32_t)t, sel);
+  if (n == 1) {
+    constexpr uint32_t SL = 64 / VM_SIGCHK_W;
+    k_vm_sigchk<<<(1 + SL - 1) / SL, 64, LDS_SIGCHK, st>>>(1, c->vm_sigchk, c->vm_consts, d, (const uint64_t*)(d + zoff), 0,
+                                                           (int32_t*)(d + zoff + 8), a.A);
+  } else {
+    k_qc_chunk<<<(N + MSM_CH - 1) >> MSM_CH_LV, 64, LDS_MSM8, st>>>(N, dtaken, c->vm_madd, c->vm_padd, MSM8_STRIDE_W,
+                                                                   c->vm_consts, a);
+    if (N > MSM_CH) k_qc_upper<<<1, 64, LDS_MSM8, st>>>(N, c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
+  }
+  k_g2p_compress<<<1, 64, 0, st>>>(a.A, d + ooff);
+  HIPCHK(hipGetLastError());
+  drain.s[1] = st;
+  HIPCHK(hipMemcpyAsync(pc.data(), dc, 4 * n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(ptk.data(), dtaken, 4 * n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(bitmap, sel.bitmap, bitmap_len, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&cnt, sel.count, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(sig96, d + ooff, 96, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  drain.armed = false;
+  CHK(pool_failed(c));
+  for (size_t j = 0; j < n; ++j) {
+    const size_t i = perm.empty() ? j : perm[j];
+    codes[i] = pc[j];
+    if (taken) taken[i] = (uint8_t)ptk[j];
+  }
+  *n_signed = cnt;
+  if (!cnt) return BLST_AGGR_TYPE_MISMATCH;
+  memcpy(out_sig, sig96, 96);
+  return 0;
+}
+
+int ovh_build_qc(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* hash, size_t hash_len, const uint8_t* pks,
+                 int32_t* codes, uint8_t* taken, uint8_t out_sig[96], uint8_t* bitmap, size_t bitmap_len,
+                 uint32_t* n_signed) {
+  if (!c || !sigs || !hash || !pks || !codes || !out_sig || !bitmap || !n_signed) return OVH_ERR_ARG;
+  if (n == 0 || n > (1u << 24)) return OVH_ERR_ARG;
+  if (hash_len != 32) return OVH_ERR_HASH_LEN;
+  std::vector<uint8_t> hashes(n * 32);  // the batch's and the verdict cache's per-vote form
+  for (size_t i = 0; i < n; ++i) memcpy(&hashes[32 * i], hash, 32);
+  int r;
+  {
+    ovh_ctx* s = c->sub.empty() ? c : c->sub[0];
+    std::lock_guard<std::mutex> g(s->mu);
+    if (!s->tab.n || bitmap_len != ((size_t)s->tab.n + 7) / 8) return OVH_ERR_ARG;
+    r = build_qc_locked(s, n, sigs, hashes.data(), pks, codes, taken, out_sig, bitmap, bitmap_len, n_signed);
+  }
+  if (r == 0 || r == BLST_AGGR_TYPE_MISMATCH) cache_put(c, n, sigs, hashes.data(), pks, codes);
+  return r;
 }
 
 int ovh_set_test_rlc(ovh_ctx* c, uint64_t seed, uint64_t index_base) {

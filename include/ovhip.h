@@ -192,6 +192,36 @@ int ovh_msg_cache_stats(ovh_ctx* ctx, uint64_t stats[2]);
 int ovh_verify_qc_batch(ovh_ctx* ctx, size_t nq, const uint8_t* sigs, const uint8_t* hashes, const uint8_t* bitmaps,
                         size_t bitmap_len, int32_t* codes);
 
+/* The leader's side of a round in one device pass: verify the round's n votes on `hash` (the
+ * SM3 of rlp(Vote), hash_len 32), select the votes that count, and aggregate their signatures
+ * into the QC that ovh_verify_qc_batch and check_block consume. Replaces, for a round, overlord's
+ * per-vote verify_signature (consensus.rs:397-416), the host's filtering and bitmap, and
+ * aggregate_signatures (consensus.rs:418-444). sigs n x 96 B, pks n x 48 B; needs
+ * ovh_set_validators. Host buffers, synchronous, thread-safe; a multi-device context runs it on
+ * its first device, as ovh_verify_qc_batch.
+ *   codes[i]   exactly the ovh_verify(sig_i, hash, pk_i) result of every vote, taken or not (the
+ *              batch check of ovh_verify_batch: secret coefficients, bisection). The verdicts enter
+ *              the verdict cache as ovh_prefetch's do.
+ *   taken[i]   (may be NULL) 1 when vote i is taken, else 0. Vote i is taken iff codes[i] == 0, its
+ *              voter is in the validator table, and no vote with a lower index is taken for the same
+ *              voter (an invalid earlier vote of a voter does not block a later valid one).
+ *   out_sig    the 96-byte compressed sum of the taken signatures.
+ *   bitmap     bitmap_len == ceil(table size / 8) bytes, MSB first over the table sorted by key
+ *              bytes (the extract_voters order, exactly what ovh_verify_qc_batch reads): one bit per
+ *              taken voter, pad bits 0. A key that occurs twice in the table counts at its first
+ *              position in sorted order.
+ *   *n_signed  the number of taken votes (every validator has weight 1; the caller compares it
+ *              with its threshold).
+ * Returns 0; BLST_AGGR_TYPE_MISMATCH (4, aggregate_signatures of an empty list) when no vote is
+ * taken -- codes, taken, a zero bitmap and *n_signed = 0 are still written, out_sig is not;
+ * OVH_ERR_HASH_LEN when hash_len != 32; OVH_ERR_ARG for a NULL pointer, no validator table, a
+ * wrong bitmap_len, n == 0 or n above the batch limit (2^24); device / RNG errors as elsewhere.
+ * On the device the signatures are parsed and subgroup-checked once (by the verify batch, whose
+ * points the sum reuses) and the host waits once, after everything is enqueued. */
+int ovh_build_qc(ovh_ctx* ctx, size_t n, const uint8_t* sigs /* n x 96 */, const uint8_t* hash, size_t hash_len,
+                 const uint8_t* pks /* n x 48 */, int32_t* codes /* n */, uint8_t* taken /* n, may be NULL */,
+                 uint8_t out_sig[96], uint8_t* bitmap, size_t bitmap_len, uint32_t* n_signed);
+
 /* TESTS ONLY (context created with OVH_FLAG_TEST_RLC, else OVH_ERR_ARG): vote i of every
  * following batch gets the coefficient SplitMix64(seed, index_base + i). Predictable
  * coefficients let an adversary cancel invalid signatures inside the combined check

@@ -245,6 +245,32 @@ impl HipCrypto {
         })?;
         Ok(codes)
     }
+
+    /// The leader's side of a round in one device pass (`ovh_build_qc`): verify the round's votes
+    /// on `hash`, take per validator its first valid vote, and aggregate the taken signatures.
+    /// Returns the QC's signature, the address bitmap (MSB first over the key-sorted table of
+    /// `update_pubkeys`, the `extract_voters` order), the per-vote codes (the per-call
+    /// `verify_signature` results, also entered in the verdict cache) and the taken flags; the
+    /// caller compares the number of taken votes with its threshold. `CryptoErr(4)` when no vote
+    /// is taken, as `aggregate_signatures` of an empty list. Blocking.
+    #[allow(clippy::type_complexity)]
+    pub fn build_qc(&self, sigs: &[[u8; 96]], hash: &[u8], voters: &[[u8; 48]]) -> Result<(Bytes, Bytes, Vec<i32>, Vec<u8>), Box<dyn Error + Send>> {
+        if sigs.len() != voters.len() {
+            return Err(to_err(ffi::OVH_ERR_LEN_MISMATCH));
+        }
+        let table = self.pubkeys.blocking_read().len();
+        let mut codes = vec![0i32; sigs.len()];
+        let mut taken = vec![0u8; sigs.len()];
+        let mut bitmap = vec![0u8; (table + 7) / 8];
+        let mut out = [0u8; 96];
+        let mut n_signed = 0u32;
+        check(unsafe {
+            ffi::ovh_build_qc(self.raw(), sigs.len(), sigs.as_ptr() as *const u8, hash.as_ptr(), hash.len(),
+                              voters.as_ptr() as *const u8, codes.as_mut_ptr(), taken.as_mut_ptr(), out.as_mut_ptr(),
+                              bitmap.as_mut_ptr(), bitmap.len(), &mut n_signed)
+        })?;
+        Ok((Bytes::copy_from_slice(&out), Bytes::from(bitmap), codes, taken))
+    }
 }
 
 impl OverlordCrypto for HipCrypto {
