@@ -4,7 +4,9 @@
 // every partial product is one v_mad_u64_u32 into a 64-bit accumulator, with no carry word
 // (the 12 x 32 product scanning pays one v_addc per v_mad). R = 2^392; a enters shifted left by
 // 8 bits, so the result is a b 2^-384 (the Montgomery form everywhere else is unchanged).
-// tools/ubench/fp_mul28.hip times it against fp_mul_gfx950 and checks them against each other.
+// tests/test_gpu_fp_bounds.py checks this form, the two asm forms of fp_mul28_gfx950.hpp and
+// fp_mul_gfx950 on the device against exact integers at the limb and range edges
+// (tests/fp_cases.py); tools/ubench/fp_mul28.hip times it against fp_mul_gfx950.
 #pragma once
 #include <stdint.h>
 

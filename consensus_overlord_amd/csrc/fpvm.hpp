@@ -9,11 +9,14 @@
 //
 // Lazy reduction. A slot holds a Montgomery representative in [0, 2p) (p < 2^381, so 2^384 >
 // 9.8 p leaves room): products take operands in [0, 4p) -- a + b or a + (2p - b) of two slots,
-// with no reduction -- and return [0, 1.625 p) after one conditional subtraction
-// ((4p)^2 / 2^384 + p < 2.63 p); linear combinations sum their terms unreduced (< 8p, times
+// with no reduction -- and return [0, 1.6253 p) after one conditional subtraction
+// (T < a b / 2^384 + p, so r = T - p < (4p)^2 / 2^384 = 16 (p / 2^384) p = 1.62527 p, or r = T
+// < p; T < 2.63 p); linear combinations sum their terms unreduced (< 8p, times
 // k <= 15 < 120p) and reduce once by a float estimate of the quotient to [0, 2p). Only the ops
 // whose result depends on the canonical value (sgn0, lex, the equality test, `st` outputs,
 // inversion) canonicalise: a product by the plain 1 of a value below 4p is at most p.
+// tests/test_fp_bounds_host.py (host build) and tests/test_gpu_fp_bounds.py (device) run each of
+// these clauses at its bounds against exact integers (tests/fp_cases.py).
 #pragma once
 #include "bls/fp.hpp"
 

@@ -100,6 +100,78 @@ void hx_fp_inv_raw(const uint32_t* a, const uint32_t* r_raw, uint32_t* out) {
   for (int k = 0; k < 12; ++k) out[k] = r.v[k];
 }
 
+// ---- the arithmetic primitives on arrays of cases (tests/fp_cases.py; the device counterparts
+// are tests/device/fp_probe.hip dp_*): n cases, 12 words per value.
+static inline Fp ld12(const uint32_t* p, uint32_t i) { return fp_const(p + (size_t)i * 12); }
+static inline void st12(uint32_t* p, uint32_t i, const Fp& v) {
+  for (int k = 0; k < 12; ++k) p[(size_t)i * 12 + k] = v.v[k];
+}
+
+// fp_mul as this build gets it: the 12 x 32 CIOS loop (a, b < 4p)
+void hx_fp_mul(uint32_t n, const uint32_t* a, const uint32_t* b, uint32_t* r) {
+  for (uint32_t i = 0; i < n; ++i) {
+    Fp m;
+    fp_mul(m, ld12(a, i), ld12(b, i));
+    st12(r, i, m);
+  }
+}
+
+// flags[i]: bit 0 ny, bit 1 any_neg
+void hx_pre_add2(uint32_t n, const uint32_t* A, const uint32_t* B, const uint32_t* C, const uint32_t* D,
+                 const uint8_t* flags, uint32_t* x, uint32_t* y) {
+  for (uint32_t i = 0; i < n; ++i) {
+    Fp X, Y;
+    ovh::vm::pre_add2(X, ld12(A, i), ld12(B, i), Y, ld12(C, i), ld12(D, i), (flags[i] & 1) != 0, (flags[i] & 2) != 0);
+    st12(x, i, X);
+    st12(y, i, Y);
+  }
+}
+
+// lin_sum + scale_reduce as exec runs them. ctl[i]: bits 0..2 the negation masks of B, C, D,
+// bits 8..11 the scale k, and the header's H_LINNEG / H_LINNEG2 / H_LINNEG3 bits in place.
+// cst: the constant table (entries KTAB + 0..4 are read).
+void hx_lin_unit(uint32_t n, const uint32_t* A, const uint32_t* B, const uint32_t* C, const uint32_t* D,
+                 const uint32_t* ctl, const uint32_t* cst, uint32_t* r) {
+  using namespace ovh::vm;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t c = ctl[i], k = (c >> 8) & 15;
+    uint32_t s[13];
+    lin_sum(s, ld12(A, i), ld12(B, i), ld12(C, i), ld12(D, i), 0u - (c & 1), 0u - ((c >> 1) & 1), 0u - ((c >> 2) & 1),
+            c & (H_LINNEG | H_LINNEG2 | H_LINNEG3), cst);
+    Fp l;
+    scale_reduce(l, s, k > 1 ? k : 1u);
+    st12(r, i, l);
+  }
+}
+
+// coefs: 4 signed bytes per case
+void hx_lin_mad(uint32_t n, const uint32_t* A, const uint32_t* B, const uint32_t* C, const uint32_t* D,
+                const int8_t* coefs, uint32_t* r) {
+  for (uint32_t i = 0; i < n; ++i) {
+    Fp l;
+    ovh::vm::lin_mad(l, ld12(A, i), ld12(B, i), ld12(C, i), ld12(D, i), coefs[4 * i], coefs[4 * i + 1],
+                     coefs[4 * i + 2], coefs[4 * i + 3]);
+    st12(r, i, l);
+  }
+}
+
+void hx_canon(uint32_t n, const uint32_t* a, uint32_t* r) {
+  for (uint32_t i = 0; i < n; ++i) {
+    Fp c;
+    ovh::vm::canon(c, ld12(a, i));
+    st12(r, i, c);
+  }
+}
+
+// hx_fp_inv_raw on an array (r3: 12 words, the same for every case)
+void hx_fp_inv(uint32_t n, const uint32_t* a, const uint32_t* r3, uint32_t* r) {
+  for (uint32_t i = 0; i < n; ++i) {
+    Fp z;
+    ovh::vm::fp_inv(z, ld12(a, i), fp_const(r3));
+    st12(r, i, z);
+  }
+}
+
 // One slice of an Fp-VM program through the interpreter (fpvm.hpp exec), lane by lane in each
 // phase (a phase's writes never target a slot that phase reads: tools/fpvm/sched.py).
 // slots: nslots x 12 words (in/out); planes: `st` output planes, 12 words each.

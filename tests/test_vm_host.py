@@ -4,92 +4,25 @@ value by value with the slot-level simulator (tools/fpvm/sched.simulate), which 
 ties to the CPU oracle on the golden votes. Both interpreter modes: each lane alone, and every
 wave-uniform block run for every lane (what a mixed wave does on the GPU)."""
 import ctypes
-import json
-import os
-import sys
 
 import numpy as np
 import pytest
 
+import fp_cases
 from test_host_harness import hx  # noqa: F401  (module fixture: builds libhx.so)
+from vm_helpers import P, R, _words, assert_same, build_all, gen, golden_vote_inputs, load_golden, run_vm, sched
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools", "fpvm"))
-
-import gen  # noqa: E402
-import progs  # noqa: E402
-import sched  # noqa: E402
-from ir import P  # noqa: E402
-
-R = pow(2, 384, P)
-RAW_INPUTS = {"pk_sort", "sig_sort"}   # flags the vote prologue writes as plain limbs
-
-
-def _words(v):
-    return [(v >> (32 * k)) & 0xFFFFFFFF for k in range(12)]
-
-
-def _int(ws):
-    return sum(int(w) << (32 * k) for k, w in enumerate(ws))
+import progs  # noqa: E402  (tools/fpvm: vm_helpers puts it on the path)
 
 
 @pytest.fixture(scope="module")
 def built():
-    return gen.build_all()
-
-
-def run_vm(hx, consts, sc, words, inputs, scalar, any_all):
-    prog = sc.prog
-    slots = np.zeros(sc.nslots * 12, dtype=np.uint32)
-    for name, v in prog.inputs.items():
-        if v in sc.slot_of:
-            val = inputs[name] % P
-            s = sc.slot_of[v]
-            slots[s * 12:s * 12 + 12] = _words(val if name in RAW_INPUTS else val * R % P)
-    code = np.asarray(words, dtype=np.uint32)
-    cst = np.asarray(consts.words(), dtype=np.uint32).ravel()
-    planes = np.zeros(64 * 12, dtype=np.uint32)
-    u32p = ctypes.POINTER(ctypes.c_uint32)
-    hx.hx_vm_run.argtypes = [u32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, ctypes.c_uint64,
-                             u32p, ctypes.c_uint32, ctypes.c_int, u32p, u32p]
-    # spilled programs (sched.spill_pass): side words and the unit's scratch
-    nscr = getattr(sc, "nscr", 0)
-    side = np.asarray(sc.side_words, dtype=np.uint32) if nscr else None
-    scr = np.zeros(max(nscr, 1) * 12, dtype=np.uint32)
-    assert hx.hx_vm_run(code.ctypes.data_as(u32p), sc.nrounds, sc.W, sched.words_per_lane(prog), cst.ctypes.data_as(u32p),
-                        slots.ctypes.data_as(u32p), scalar, planes.ctypes.data_as(u32p), 64, any_all,
-                        side.ctypes.data_as(u32p) if side is not None else None, scr.ctypes.data_as(u32p)) == 0
-    out = {}
-    for name, v in prog.outputs.items():
-        op = prog.ops[v]
-        if op.kind == "st":
-            out[name] = _int(planes[op.imm * 12:op.imm * 12 + 12])
-        else:
-            s = sc.slot_of[v]
-            out[name] = _int(slots[s * 12:s * 12 + 12])
-    return out
-
-
-def assert_same(dev, sim, what):
-    for name, s in sim.items():
-        d = dev[name]
-        # a Montgomery representative in [0, 2p) (canonical for `st` planes) or a raw flag
-        ok = (d % P == s * R % P and d < (P if name.startswith("st:") else 2 * P)) or (s in (0, 1) and d == s)
-        assert ok, "%s: output %s interpreter %x, simulator %x" % (what, name, d, s)
+    return build_all()
 
 
 @pytest.fixture(scope="module")
 def golden_votes():
-    with open(os.path.join(ROOT, "tests", "golden", "golden_v1.json")) as fh:
-        g = json.load(fh)
-    bls = gen._oracle()
-    out = []
-    for v, k in list(zip(g["votes"], g["keys"]))[:2]:
-        out.append(gen.vote_inputs(bls, bytes.fromhex(k["pk"]), bytes.fromhex(v["sig"]), bytes.fromhex(v["digest"])))
-    bad = [c for c in g["verify"] if c["code"] == 3 and len(c["sig"]) == 192 and len(c["pk"]) == 96]
-    for c in bad[:1]:
-        out.append(gen.vote_inputs(bls, bytes.fromhex(c["pk"]), bytes.fromhex(c["sig"]), bytes.fromhex(c["hash"])))
-    return out
+    return golden_vote_inputs()
 
 
 @pytest.mark.parametrize("any_all", [0, 1])
@@ -111,8 +44,7 @@ def test_vote_t_program_on_interpreter(hx, built, golden_votes, any_all):  # noq
     _, vsc, vwords, _, _ = progs_["vote"]
     prog, sc, words, _, _ = progs_["vote_t"]
     bls = gen._oracle()
-    with open(os.path.join(ROOT, "tests", "golden", "golden_v1.json")) as fh:
-        g = json.load(fh)
+    g = load_golden()
     r = 0x0F1E2D3C4B5A6978
     for k, inp in enumerate(golden_votes[:2]):
         pk = bls.g1_from_bytes(bytes.fromhex(g["keys"][k]["pk"]))
@@ -173,8 +105,7 @@ def test_msm_programs_on_interpreter(hx, built, golden_votes, any_all):  # noqa:
     values to the oracle's point arithmetic)."""
     consts, progs_ = built
     bls = gen._oracle()
-    with open(os.path.join(ROOT, "tests", "golden", "golden_v1.json")) as fh:
-        g = json.load(fh)
+    g = load_golden()
     A, B = (bls.g2_from_bytes(bytes.fromhex(v["sig"])) for v in g["votes"][:2])
     for name, (prog, sc, words, ins, outs) in progs_.items():
         if name not in ("madd", "padd") and not name.startswith("hdbl"):
@@ -194,11 +125,7 @@ def test_fp_inv(hx):
     u32p = ctypes.POINTER(ctypes.c_uint32)
     hx.hx_fp_inv_raw.argtypes = [u32p, u32p, u32p]
     rr = np.array(_words(R), dtype=np.uint32)
-    rng = np.random.default_rng(0xB1A5)
-    vals = [0, 1, 2, 3, P - 1, P - 2, (P - 1) // 2, (P + 1) // 2, 2 ** 380, 2 ** 381 - 1 - P + P // 3,
-            (1 << 32) - 1, 1 << 200, P - (1 << 300)]
-    vals += [int.from_bytes(rng.bytes(48), "little") % P for _ in range(400)]
-    vals += [int.from_bytes(rng.bytes(48), "little") % (1 << int(rng.integers(1, 381))) for _ in range(100)]
+    vals = fp_cases.fp_inv_values()
     for a in vals:
         a %= P
         out = np.zeros(12, dtype=np.uint32)
@@ -217,8 +144,7 @@ def test_percall_programs_on_interpreter(hx, built, golden_votes, any_all):  # n
     the oracle: decompressed points, sums, the golden signature, the pairing verdict)."""
     consts, progs_ = built
     bls = gen._oracle()
-    with open(os.path.join(ROOT, "tests", "golden", "golden_v1.json")) as fh:
-        g = json.load(fh)
+    g = load_golden()
 
     def run(name, inp, scalar=0):
         _, sc, words, _, _ = progs_[name]
@@ -265,8 +191,7 @@ def test_samemsg_programs_on_interpreter(hx, built, golden_votes, any_all):  # n
     loop of the key sum, pkdec's key validation)."""
     consts, progs_ = built
     bls = gen._oracle()
-    with open(os.path.join(ROOT, "tests", "golden", "golden_v1.json")) as fh:
-        g = json.load(fh)
+    g = load_golden()
     if any_all == 0:
         gen.check_samemsg(progs_, bls, g)
     r = 0xC2B2AE3D27D4EB4F
