@@ -373,6 +373,10 @@ VM_FN int coef5(uint32_t w, int lo) { return ((int)(w << (27 - lo))) >> 27; }
 // r06: only what every phase needs is decoded up front (the header, the opcode, the four operand
 // addresses); each block extracts its own fields (dst, coefficient signs, scale, imm), so a
 // product phase no longer pays for the linear blocks' decoding (r05: 10 VALU per phase).
+// INV: whether the interpreter carries the inversion (the divsteps loop and its products, about a
+// third of exec's code). Only programs with an `inv` op need it (VM_<PROG>_HAS_INV, vm_progs.inc);
+// without it an `inv` op stores its operand unchanged, so a kernel static_asserts on its program.
+template <bool INV = true>
 VM_FN void exec(const uint4 in, bool active, uint32_t* __restrict__ slots, const uint32_t* __restrict__ cst,
                 uint64_t scalar, const Out& out) {
   // the phase header (bits 22.. of w0, equal in every lane; tools/fpvm/sched.py phase_bits) names
@@ -448,12 +452,10 @@ VM_FN void exec(const uint4 in, bool active, uint32_t* __restrict__ slots, const
       z = A.v[0] ? C : B;
     } else if (op >= OP_AND && op <= OP_XOR) {
       set_flag(z, op == OP_AND ? (A.v[0] & C.v[0]) : op == OP_OR ? (A.v[0] | C.v[0]) : (A.v[0] ^ C.v[0]));
-    } else if (op == OP_INV) {
-#ifndef OVH_VM_NO_INV
+    } else if (INV && op == OP_INV) {
       Fp a;
       canon(a, A);
       fp_inv(z, a, C);
-#endif
     }
     if (rare && op != OP_ST) st_slot(slots, dst, z);
   }
@@ -497,12 +499,22 @@ __device__ __forceinline__ void side_spill(uint32_t sw, uint32_t* __restrict__ s
   }
 }
 
-template <bool SIDE = false>
+// Loop shape of run(): 3 = unrolled three times over three-register rings (no register copies,
+// three inlined copies of exec); 1 = one copy of exec, the prefetched words rotated by register
+// moves (4 for the instruction, 2 for the side words). A kernel's code size is mostly its copies
+// of exec. The default is the one copy; the vote pool's loop, the throughput stage,
+// asks for 3 (ovhip.hip OVH_POOL_UNROLL).
+#ifndef OVH_VM_UNROLL
+#define OVH_VM_UNROLL 1
+#endif
+
+template <bool SIDE = false, bool INV = true, int UNROLL = OVH_VM_UNROLL>
 __device__ __forceinline__ void run(const uint4* __restrict__ code, uint32_t nphases, uint32_t W, uint32_t lane,
                                     bool active, uint32_t* __restrict__ slots, const uint32_t* __restrict__ cst,
                                     uint64_t scalar, const Out& out, uint64_t* __restrict__ trace = nullptr,
                                     const uint32_t* __restrict__ side = nullptr, uint32_t* __restrict__ scr = nullptr) {
   static_assert(PREFETCH >= 5, "the unrolled loops below read up to 4 phases past the end");
+  static_assert(UNROLL == 1 || UNROLL == 3, "loop shapes: 1 (rotated by moves) or 3 (unrolled over the rings)");
   if constexpr (SIDE) {
     // r06: the loop is unrolled three times over three-register rings. At the start of phase ph
     // the words of phase ph + 2 load into the registers that held phase ph - 1's (no register
@@ -511,8 +523,9 @@ __device__ __forceinline__ void run(const uint4* __restrict__ code, uint32_t nph
     // next phase's fill first), so whatever the compiler waits for at the next phase's start has
     // had a whole phase. A partial last round runs up to two of the code's trailing NOP phases
     // (no ops, zero side words).
-    uint4 qa = code[lane], qb = code[W + lane], qc;
+    uint4 qa = code[lane], qb, qc;
     uint32_t sa = side[lane], sb = side[W + lane], sc;
+    if constexpr (UNROLL == 3) qb = code[W + lane];
     // inactive lanes (a slice past the batch's end) run no side op: their unit has no scratch
     if (!active) sa = sb = 0;
     // the first words complete before the loop: the compiler loads them straight into the loop's
@@ -520,9 +533,10 @@ __device__ __forceinline__ void run(const uint4* __restrict__ code, uint32_t nph
     // its own fresh prefetch (r06 ISA)
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
     // phase ph: instruction q, side word s, the next phase's side word sn (its fill is issued
-    // now); q2 / s2 take phase ph + 2's words
+    // now); q2 takes the instruction of phase ph + QD, s2 the side word of phase ph + 2
     auto step = [&](const uint4& q, uint4& q2, const uint32_t s, const uint32_t sn, uint32_t& s2,
                     const uint32_t ph) __attribute__((always_inline)) {
+      constexpr uint32_t QD = UNROLL == 3 ? 2 : 1;
       const bool fill = (sn & (SIDE_VALID | SIDE_FILL)) == (SIDE_VALID | SIDE_FILL);
       u32x4 f0, f1, f2;
       if (fill) {
@@ -531,9 +545,9 @@ __device__ __forceinline__ void run(const uint4* __restrict__ code, uint32_t nph
         f1 = __builtin_nontemporal_load(src + 1);
         f2 = __builtin_nontemporal_load(src + 2);
       }
-      q2 = code[(size_t)(ph + 2) * W + lane];
+      q2 = code[(size_t)(ph + QD) * W + lane];
       s2 = active ? side[(size_t)(ph + 2) * W + lane] : 0u;
-      exec(q, active, slots, cst, scalar, out);
+      exec<INV>(q, active, slots, cst, scalar, out);
       // this phase's spill reads its slot before the fill lands: a fill may take the slot of a
       // value whose last read is this spill
       side_spill(s, slots, scr);
@@ -544,11 +558,23 @@ __device__ __forceinline__ void run(const uint4* __restrict__ code, uint32_t nph
         d[2] = f2;
       }
     };
+    if constexpr (UNROLL == 3) {
 #pragma unroll 1
-    for (uint32_t ph = 0; ph < nphases; ph += 3) {
-      step(qa, qc, sa, sb, sc, ph);
-      step(qb, qa, sb, sc, sa, ph + 1);
-      step(qc, qb, sc, sa, sb, ph + 2);
+      for (uint32_t ph = 0; ph < nphases; ph += 3) {
+        step(qa, qc, sa, sb, sc, ph);
+        step(qb, qa, sb, sc, sa, ph + 1);
+        step(qc, qb, sc, sa, sb, ph + 2);
+      }
+    } else {
+      // one copy of exec: the next phase's instruction loads at the start of this one (the side
+      // words stay two ahead, a fill is issued a phase early) and the rings rotate by moves
+#pragma unroll 1
+      for (uint32_t ph = 0; ph < nphases; ++ph) {
+        step(qa, qb, sa, sb, sc, ph);
+        qa = qb;
+        sa = sb;
+        sb = sc;
+      }
     }
     __asm__ volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     return;
@@ -556,22 +582,32 @@ __device__ __forceinline__ void run(const uint4* __restrict__ code, uint32_t nph
   // trace (diagnostics, OVH_FLAG_VM_TRACE): wall clock after every phase
   if (trace && threadIdx.x == 0) trace[0] = wall_clock64();
   // unrolled three times over a three-register ring, phase ph + 2's words loaded at the start of
-  // phase ph (as the side-word loop above); a partial last round runs trailing NOP phases
-  uint4 qa = code[lane], qb = code[W + lane], qc;
+  // phase ph (as the side-word loop above); a partial last round runs trailing NOP phases.
+  // UNROLL == 1: phase ph + 1's words, one move of the instruction per phase
+  uint4 qa = code[lane], qb, qc;
+  if constexpr (UNROLL == 3) qb = code[W + lane];
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), as above
   auto step = [&](const uint4& q, uint4& q2, const uint32_t ph) __attribute__((always_inline)) {
-    q2 = code[(size_t)(ph + 2) * W + lane];
-    exec(q, active, slots, cst, scalar, out);
+    q2 = code[(size_t)(ph + (UNROLL == 3 ? 2 : 1)) * W + lane];
+    exec<INV>(q, active, slots, cst, scalar, out);
     if (trace && ph < nphases) {
       __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       if (threadIdx.x == 0) trace[ph + 1] = wall_clock64();
     }
   };
+  if constexpr (UNROLL == 3) {
 #pragma unroll 1
-  for (uint32_t ph = 0; ph < nphases; ph += 3) {
-    step(qa, qc, ph);
-    step(qb, qa, ph + 1);
-    step(qc, qb, ph + 2);
+    for (uint32_t ph = 0; ph < nphases; ph += 3) {
+      step(qa, qc, ph);
+      step(qb, qa, ph + 1);
+      step(qc, qb, ph + 2);
+    }
+  } else {
+#pragma unroll 1
+    for (uint32_t ph = 0; ph < nphases; ++ph) {
+      step(qa, qb, ph);
+      qa = qb;
+    }
   }
   // the caller reads results through LDS (other lanes' slots) and may reuse it
   __asm__ volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");

@@ -213,7 +213,7 @@ __device__ __forceinline__ void msm_pair_op(const VmDev& prog, uint32_t nin, uin
     }
   }
   __syncthreads();
-  vm::run(prog.code, prog.nphases, W, lane, active, slots, cst, 0, vm::Out{nullptr, 0, 0});
+  vm::run<false, false>(prog.code, prog.nphases, W, lane, active, slots, cst, 0, vm::Out{nullptr, 0, 0});
   if (active) {
     const Slab& d = kd == SRC_U ? a.U : a.A;
     for (uint32_t k = lane; k < 6; k += W) {

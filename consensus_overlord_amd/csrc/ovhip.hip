@@ -50,6 +50,18 @@
 #include <vm_progs.inc>  // generated (tools/fpvm/gen.py): -Icsrc (Makefile) or -I OUT_DIR (overlord-hip/build.rs)
 #endif
 static_assert(VM_KZERO == ovh::vm::KZERO && VM_KTAB == ovh::vm::KTAB, "fixed constants (tools/fpvm/gen.py)");
+// The inversion's code goes only into the kernels whose program has an `inv` op (vm::run's INV
+// parameter; VM_<PROG>_HAS_INV from the generator): the three final-exponentiation programs. A
+// kernel that binds a program to the interpreter without it says so where it calls vm::run.
+#define VM_ASSERT_NO_INV(P) static_assert(!VM_##P##_HAS_INV, #P " has an inv op: it needs vm::run<SIDE, true>")
+#define VM_ASSERT_INV(P) static_assert(VM_##P##_HAS_INV, #P " has no inv op: bind it to vm::run<SIDE, false>")
+// the programs that reach kernels through a VmDev chosen by the host (MSM and tree adds, the
+// per-vote programs of the small-batch and same-message paths)
+VM_ASSERT_NO_INV(MADD); VM_ASSERT_NO_INV(PADD); VM_ASSERT_NO_INV(G1PADD);
+VM_ASSERT_NO_INV(HDBL1); VM_ASSERT_NO_INV(HDBL2); VM_ASSERT_NO_INV(HDBL4); VM_ASSERT_NO_INV(HDBL8); VM_ASSERT_NO_INV(HDBL16);
+VM_ASSERT_NO_INV(VOTE1); VM_ASSERT_NO_INV(VOTE_T1); VM_ASSERT_NO_INV(VOTE1H); VM_ASSERT_NO_INV(VOTE_T1H);
+VM_ASSERT_NO_INV(VOTEW); VM_ASSERT_NO_INV(VOTEW_T);
+VM_ASSERT_NO_INV(VSAME); VM_ASSERT_NO_INV(VSAME_T); VM_ASSERT_NO_INV(VSAME8); VM_ASSERT_NO_INV(VSAME8_T);
 
 using namespace ovh;
 
@@ -289,6 +301,7 @@ __device__ __forceinline__ uint32_t slot_flag_get(const uint32_t* slots, uint32_
 // identity); with codes (level 0) every vote whose code is not 0 contributes the identity.
 // inS.p null: every S is the identity (the batch path's S is the MSM's, msm.hpp).
 // All 64 threads of the workgroup call it (the phase barrier); `active` marks the working slice.
+template <int UNROLL = OVH_VM_UNROLL>
 __device__ __forceinline__ void fold_unit(uint32_t t, uint32_t m, const VmDev& prog, const uint32_t* cst,
                                           uint32_t* slots, uint32_t lane, bool active, Slab inF, Slab inS,
                                           Slab out, const int32_t* __restrict__ codes) {
@@ -308,7 +321,9 @@ __device__ __forceinline__ void fold_unit(uint32_t t, uint32_t m, const VmDev& p
     }
   }
   __syncthreads();
-  vm::run(prog.code, VM_FOLD_NPHASES, VM_FOLD_W, lane, active, slots, cst, 0, vm::Out{nullptr, 0, 0});
+  VM_ASSERT_NO_INV(FOLD);
+  vm::run<false, false, UNROLL>(prog.code, VM_FOLD_NPHASES, VM_FOLD_W, lane, active, slots, cst, 0,
+                                vm::Out{nullptr, 0, 0});
   if (active) {
     for (uint32_t k = lane; k < PART_PLANES; k += VM_FOLD_W) {
       Fp v;
@@ -676,11 +691,22 @@ __device__ __forceinline__ T* unip(T* p) {
 // (fused: -> partial `quad` of R0, the identity for failed votes). Only the VM's own operands
 // stay in registers across the program: the slot and quad wait in the LDS header words of slice
 // 2 and the clock stamps (OVH_FLAG_VM_CLOCK) in those of slices 0 and 1.
-template <bool TABLE>
-__device__ __forceinline__ void vote_quad(const PoolArgs& a, uint32_t slot_in, uint32_t quad_in, uint32_t* lds) {
-  constexpr uint32_t NSLOTS = TABLE ? VM_VOTE_T_NSLOTS : VM_VOTE_NSLOTS;
-  constexpr uint32_t STRIDE = TABLE ? VOTE_T_STRIDE_W : VOTE_STRIDE_W;
-  constexpr uint32_t NPH = TABLE ? VM_VOTE_T_NPHASES : VM_VOTE_NPHASES;
+// TABLE (wave-uniform: the batch's keys come from the validator table, program vote_t, or as
+// bytes, program vote) picks the slot count, stride, phase count, maps, code and side words, the
+// prologue and the epilogue -- all values or uniform branches around the one interpreter loop
+// both kinds of quad go through (two instantiations doubled the kernel's code).
+// The pool's vote loop is the throughput stage: it keeps the loop unrolled over its register
+// rings whatever OVH_VM_UNROLL gives the other kernels (A/B: DESIGN 4.7).
+#ifndef OVH_POOL_UNROLL
+#define OVH_POOL_UNROLL 3
+#endif
+__device__ __forceinline__ void vote_quad(const PoolArgs& a, uint32_t slot_in, uint32_t quad_in, uint32_t* lds,
+                                          const bool TABLE) {
+  VM_ASSERT_NO_INV(VOTE);
+  VM_ASSERT_NO_INV(VOTE_T);
+  const uint32_t NSLOTS = TABLE ? VM_VOTE_T_NSLOTS : VM_VOTE_NSLOTS;
+  const uint32_t STRIDE = TABLE ? VOTE_T_STRIDE_W : VOTE_STRIDE_W;
+  const uint32_t NPH = TABLE ? VM_VOTE_T_NPHASES : VM_VOTE_NPHASES;
   const uint16_t* IN = TABLE ? VM_VOTE_T_IN : VM_VOTE_IN;
   const uint16_t* OUT = TABLE ? VM_VOTE_T_OUT : VM_VOTE_OUT;
   uint32_t* cst = lds;
@@ -721,7 +747,7 @@ __device__ __forceinline__ void vote_quad(const PoolArgs& a, uint32_t slot_in, u
     }
     __syncthreads();
     if (active) {
-      if constexpr (TABLE) {
+      if (TABLE) {
         const int32_t* idx = reinterpret_cast<const int32_t*>(sigs + (size_t)n * 144);
         const uint32_t e = uni(dget(&bd->has_idx)) ? (uint32_t)idx[i] : i;
         if (lane == 1) {
@@ -752,9 +778,10 @@ __device__ __forceinline__ void vote_quad(const PoolArgs& a, uint32_t slot_in, u
     }
     __syncthreads();
     const uint64_t scalar = vote_scalar(uni64(dget(&bd->seed)), uni64(dget(&bd->base)), i);
-    vm::run<true>(TABLE ? a.pt_code : a.pv_code, NPH, VM_VOTE_W, lane, active, slots, cst, scalar,
-                  vm::Out{s.p, s.cap, i}, nullptr, TABLE ? a.pt_side : a.pv_side,
-                  a.scr + (size_t)blockIdx.x * VM_SLICES * VOTE_NSCR * 12 + slice * VOTE_NSCR * 12);
+    vm::run<true, false, OVH_POOL_UNROLL>(
+        TABLE ? a.pt_code : a.pv_code, NPH, VM_VOTE_W, lane, active, slots, cst, scalar, vm::Out{s.p, s.cap, i},
+        nullptr, TABLE ? a.pt_side : a.pv_side,
+        a.scr + (size_t)blockIdx.x * VM_SLICES * VOTE_NSCR * 12 + slice * VOTE_NSCR * 12);
   }
   // after the program: the slot and quad back from LDS (run ends with an LDS wait + barrier)
   const uint32_t slot = uni(park[0]), quad = uni(park[1]) & 0x0FFFFFFFu, how = uni(park[1]) >> 28;
@@ -778,7 +805,7 @@ __device__ __forceinline__ void vote_quad(const PoolArgs& a, uint32_t slot_in, u
     // consensus.rs:397-416: pk parse (102) > sig parse (1..3) > [core_verify] sig group (3) >
     // pk infinity (6) > pk group (3) > H(m) = O or sig = O (5) > pairing (batch)
     uint32_t pk_parse, pk_inf, pk_grp;
-    if constexpr (TABLE) {
+    if (TABLE) {
       pk_parse = pf & PKF_PARSE;
       pk_inf = pf & PKF_INF;
       pk_grp = !(pf & PKF_GRP);
@@ -817,7 +844,9 @@ __device__ __forceinline__ void vote_quad(const PoolArgs& a, uint32_t slot_in, u
   const Slab s{unip(dgetp(&bd->state)), uni(dget(&bd->cap))};
   VmDev fold{};
   fold.code = a.fold_code;
-  fold_unit(quad, n, fold, cst, lds + SLOT_BASE_W, threadIdx.x % VM_FOLD_W, threadIdx.x < VM_FOLD_W,
+  // (the fold's 17 phases per quad take the one-copy loop whatever OVH_VM_UNROLL says: it is a
+  // second loop in this kernel)
+  fold_unit<1>(quad, n, fold, cst, lds + SLOT_BASE_W, threadIdx.x % VM_FOLD_W, threadIdx.x < VM_FOLD_W,
             Slab{s.p + (size_t)S_F * 12 * s.cap, s.cap}, Slab{nullptr, 0},
             Slab{unip(dgetp(&bd->part0)), uni(dget(&bd->part_cap))}, codes);
   if (pl) {  // the quad's pool-log record, ahead of the release below
@@ -855,8 +884,7 @@ __global__ __launch_bounds__(64, 2) void k_vm_pool(PoolArgs a) {
     slot = uni(slot);
     quad = uni(quad) | uni(how) << 28;  // the claim's flags ride in the top bits to the pool log
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // this batch's descriptor and inputs, fresh
-    if (uni(dget(&a.descs[slot].table))) vote_quad<true>(a, slot, quad, lds);
-    else vote_quad<false>(a, slot, quad, lds);
+    vote_quad(a, slot, quad, lds, uni(dget(&a.descs[slot].table)) != 0);
   }
   if (a.wlog && threadIdx.x == 0 && blockIdx.x < PLOG_WGS) {
     uint64_t* w = a.wlog + (size_t)blockIdx.x * PLOG_WG_WORDS;
@@ -950,8 +978,12 @@ __global__ __launch_bounds__(64) void k_vm_final(uint32_t m, VmDev prog, const u
     slot_put(slots, VM_FINAL_IN[k], v.v);
   }
   __syncthreads();
-  vm::run(prog.code, VM_FINAL_NPHASES, VM_FINAL_W, lane, true, slots, cst, 0, vm::Out{nullptr, 0, 0},
-          blockIdx.x == 0 ? prog.trace : nullptr);
+  VM_ASSERT_INV(FINAL);
+  // the batch's final check is one wave on the critical path of the batch latency: it keeps the
+  // unrolled loop, whose instruction words load two phases ahead (the one-copy loop's load one
+  // phase ahead showed in stage_ms.final, 1.91 -> 2.00 ms)
+  vm::run<false, true, 3>(prog.code, VM_FINAL_NPHASES, VM_FINAL_W, lane, true, slots, cst, 0, vm::Out{nullptr, 0, 0},
+                          blockIdx.x == 0 ? prog.trace : nullptr);
   if (lane == 0) *result = slot_flag_get(slots, VM_FINAL_OUT[0]) ? 1 : 0;
 }
 
@@ -1027,7 +1059,7 @@ __device__ __forceinline__ void vote_wave(const VmDev& prog, uint32_t nph, uint3
     if constexpr (TABLE) slot_put(slots, IN[VM_VOTE_T1_IN_PK_X + (lane - 6)], v.v);
   }
   __syncthreads();
-  vm::run(prog.code, nph, 64, lane, true, slots, cst, scalar, vm::Out{s.p, s.cap, i});
+  vm::run<false, false>(prog.code, nph, 64, lane, true, slots, cst, scalar, vm::Out{s.p, s.cap, i});
   if (lane == 0) {
     const uint32_t sf = hdr[0], pf = hdr[1];
     const uint32_t sg_bad = sf & 1, sg_inf = (sf >> 1) & 1, sg_xz = (sf >> 2) & 1;
@@ -1205,7 +1237,8 @@ __global__ __launch_bounds__(64) void k_vm_vsame(uint32_t cnt, uint32_t lo, VmDe
   __syncthreads();
   constexpr uint32_t NPH = W8 ? (TABLE ? VM_VSAME8_T_NPHASES : VM_VSAME8_NPHASES)
                               : (TABLE ? VM_VSAME_T_NPHASES : VM_VSAME_NPHASES);
-  vm::run(prog.code, NPH, W, lane, active, slots, cst, vote_scalar(seed, base, i), vm::Out{s.p, s.cap, i});
+  vm::run<false, false>(prog.code, NPH, W, lane, active, slots, cst, vote_scalar(seed, base, i),
+                        vm::Out{s.p, s.cap, i});
   if (active && lane == 0) {
     const uint32_t sf = hdr[0], pf = hdr[1];
     const uint32_t sg_bad = sf & 1, sg_inf = (sf >> 1) & 1, sg_xz = (sf >> 2) & 1;
@@ -1253,7 +1286,8 @@ __global__ __launch_bounds__(64) void k_vm_h2g(uint32_t G, VmDev prog, const uin
     slot_put(slots, VM_H2G_IN[lane], u.v);
   }
   __syncthreads();
-  vm::run(prog.code, VM_H2G_NPHASES, 16, lane, active, slots, cst, 0, vm::Out{g.p, g.cap, q});
+  VM_ASSERT_NO_INV(H2G);
+  vm::run<false, false>(prog.code, VM_H2G_NPHASES, 16, lane, active, slots, cst, 0, vm::Out{g.p, g.cap, q});
   if (active && lane == 0) ghinf[q] = slot_flag_get(slots, VM_H2G_OUT[VM_H2G_OUT_H_INF]) ? 1u : 0u;
 }
 
@@ -1301,7 +1335,7 @@ __global__ __launch_bounds__(64) void k_vm_g1pairs(uint32_t npairs, VmDev prog, 
     }
   }
   __syncthreads();
-  vm::run(prog.code, prog.nphases, W, lane, active, slots, cst, 0, vm::Out{nullptr, 0, 0});
+  vm::run<false, false>(prog.code, prog.nphases, W, lane, active, slots, cst, 0, vm::Out{nullptr, 0, 0});
   if (active) {
     for (uint32_t k = lane; k < 3; k += W) {
       Fp v;
@@ -1372,7 +1406,8 @@ __global__ __launch_bounds__(64) void k_vm_gmil(uint32_t G, const uint32_t* __re
     }
     return;
   }
-  vm::run(prog.code, VM_GMIL_NPHASES, 64, lane, true, slots, cst, 0, vm::Out{g.p, g.cap, oq});
+  VM_ASSERT_NO_INV(GMIL);
+  vm::run<false, false>(prog.code, VM_GMIL_NPHASES, 64, lane, true, slots, cst, 0, vm::Out{g.p, g.cap, oq});
 }
 
 // The bisection of a same-message batch whose combined check failed (skipped when *verdict == 1):
@@ -1446,7 +1481,8 @@ __global__ __launch_bounds__(64) void k_vm_gfin(VmDev prog, const uint32_t* __re
     if (lane == 0) *verdict = 0;
     return;
   }
-  vm::run(prog.code, VM_GFIN_NPHASES, 64, lane, true, slots, cst, 0, vm::Out{nullptr, 0, 0});
+  VM_ASSERT_INV(GFIN);
+  vm::run<false, true>(prog.code, VM_GFIN_NPHASES, 64, lane, true, slots, cst, 0, vm::Out{nullptr, 0, 0});
   if (lane == 0) *verdict = slot_flag_get(slots, VM_GFIN_OUT[0]) ? 1 : 0;
 }
 
@@ -1477,7 +1513,8 @@ __global__ __launch_bounds__(64) void k_vm_qcpre(VmDev prog, const uint32_t* __r
     slot_put(slots, VM_QCPRE_IN[VM_QCPRE_IN_U00 + (lane - 2)], u.v);
   }
   __syncthreads();
-  vm::run(prog.code, VM_QCPRE_NPHASES, VM_QCPRE_W, lane, true, slots, cst, 0, vm::Out{s.p, s.cap, 0});
+  VM_ASSERT_NO_INV(QCPRE);
+  vm::run<false, false>(prog.code, VM_QCPRE_NPHASES, VM_QCPRE_W, lane, true, slots, cst, 0, vm::Out{s.p, s.cap, 0});
   if (lane == 0)
     *flags = hdr[0] | slot_flag_get(slots, VM_QCPRE_OUT[VM_QCPRE_OUT_SIG_OK]) << 8 |
              slot_flag_get(slots, VM_QCPRE_OUT[VM_QCPRE_OUT_SIG_GRP]) << 9 |
@@ -1503,7 +1540,8 @@ __global__ __launch_bounds__(64) void k_vm_qcmil(VmDev prog, const uint32_t* __r
     slot_put(slots, VM_QCMIL_IN[lane], v.v);
   }
   __syncthreads();
-  vm::run(prog.code, VM_QCMIL_NPHASES, VM_QCMIL_W, lane, true, slots, cst, 0, vm::Out{s.p, s.cap, 1});
+  VM_ASSERT_NO_INV(QCMIL);
+  vm::run<false, false>(prog.code, VM_QCMIL_NPHASES, VM_QCMIL_W, lane, true, slots, cst, 0, vm::Out{s.p, s.cap, 1});
   if (lane == 0) {
     const uint32_t sf = *flags, kf = pk.flags[0];
     const uint32_t sg_bad = sf & 1, sg_inf = (sf >> 1) & 1, sg_xz = (sf >> 2) & 1;
@@ -1536,7 +1574,8 @@ __device__ __forceinline__ bool fe_one(const VmDev& prog, const uint32_t* __rest
     slot_put(slots, VM_FINAL1_IN[lane], v.v);
   }
   __syncthreads();
-  vm::run(prog.code, VM_FINAL1_NPHASES, VM_FINAL1_W, lane, true, slots, cst, 0, vm::Out{nullptr, 0, 0});
+  VM_ASSERT_INV(FINAL1);
+  vm::run<false, true>(prog.code, VM_FINAL1_NPHASES, VM_FINAL1_W, lane, true, slots, cst, 0, vm::Out{nullptr, 0, 0});
   return slot_flag_get(slots, VM_FINAL1_OUT[0]) != 0;
 }
 
@@ -1598,7 +1637,8 @@ __device__ __forceinline__ bool final_one(uint32_t u, const VmDev& prog, const u
     slot_put(slots, VM_FINAL_IN[k], v.v);
   }
   __syncthreads();
-  vm::run(prog.code, VM_FINAL_NPHASES, VM_FINAL_W, lane, true, slots, cst, 0, vm::Out{nullptr, 0, 0});
+  VM_ASSERT_INV(FINAL);
+  vm::run<false, true>(prog.code, VM_FINAL_NPHASES, VM_FINAL_W, lane, true, slots, cst, 0, vm::Out{nullptr, 0, 0});
   return slot_flag_get(slots, VM_FINAL_OUT[0]) != 0;
 }
 
@@ -1651,8 +1691,9 @@ __global__ __launch_bounds__(64) void k_vm_rs(uint32_t n, VmDev prog, const uint
     slot_put(slots, VM_RS_IN[lane], v.v);
   }
   __syncthreads();
-  vm::run(prog.code, VM_RS_NPHASES, VM_RS_W, lane, active, slots, cst, vote_scalar(seed, base, i),
-          vm::Out{s.p, s.cap, i});
+  VM_ASSERT_NO_INV(RS);
+  vm::run<false, false>(prog.code, VM_RS_NPHASES, VM_RS_W, lane, active, slots, cst, vote_scalar(seed, base, i),
+                        vm::Out{s.p, s.cap, i});
 }
 
 #define GROUPCHECK_FAIL (0x100 | BLST_POINT_NOT_IN_GROUP)
@@ -1681,7 +1722,8 @@ __global__ __launch_bounds__(64) void k_vm_sigchk(uint32_t n, VmDev prog, const 
     hdr[0] = bad | inf << 1 | xz << 2;
   }
   __syncthreads();
-  vm::run(prog.code, VM_SIGCHK_NPHASES, VM_SIGCHK_W, lane, active, slots, cst, 0, vm::Out{nullptr, 0, 0});
+  VM_ASSERT_NO_INV(SIGCHK);
+  vm::run<false, false>(prog.code, VM_SIGCHK_NPHASES, VM_SIGCHK_W, lane, active, slots, cst, 0, vm::Out{nullptr, 0, 0});
   __syncthreads();
   if (!active) return;
   const uint32_t pf = hdr[0];
@@ -1734,7 +1776,7 @@ __global__ __launch_bounds__(64) void k_vm_g2tree(uint32_t m, VmDev prog, uint32
     }
   }
   __syncthreads();
-  vm::run(prog.code, prog.nphases, W, lane, active, slots, cst, 0, vm::Out{nullptr, 0, 0});
+  vm::run<false, false>(prog.code, prog.nphases, W, lane, active, slots, cst, 0, vm::Out{nullptr, 0, 0});
   if (active) {
     for (uint32_t k = lane; k < 6; k += W) {
       Fp v;
@@ -1793,7 +1835,8 @@ __global__ __launch_bounds__(64) void k_vm_pkgen(uint32_t n, VmDev prog, const u
   for (int r = 0; r < 4; ++r) {
     if (active && lane < 3) slot_put(slots, VM_PKGEN_IN[lane], acc + lane * 12);
     __syncthreads();
-    vm::run(prog.code, VM_PKGEN_NPHASES, W, lane, active, slots, cst, k[r], vm::Out{nullptr, 0, 0});
+    VM_ASSERT_NO_INV(PKGEN);
+    vm::run<false, false>(prog.code, VM_PKGEN_NPHASES, W, lane, active, slots, cst, k[r], vm::Out{nullptr, 0, 0});
     __syncthreads();
     if (active && lane < 3) {
       Fp t;
@@ -1916,7 +1959,10 @@ __global__ __launch_bounds__(64) void k_vm_signg(uint32_t n, VmDev p0, VmDev p1,
   uint64_t d[4] = {0, 0, 0, 0};
   if (active)
     for (int j = 0; j < 4; ++j) d[j] = dig[j];
-  vm::run(p0.code, VM_SIGNG0_NPHASES, W, lane, active, slots, cst, signg_scalar(d, 0), vm::Out{nullptr, 0, 0});
+  VM_ASSERT_NO_INV(SIGNG0);
+  VM_ASSERT_NO_INV(SIGNG1);
+  vm::run<false, false>(p0.code, VM_SIGNG0_NPHASES, W, lane, active, slots, cst, signg_scalar(d, 0),
+                        vm::Out{nullptr, 0, 0});
   __syncthreads();
   if (active)
     for (uint32_t q = lane; q < 96; q += W)
@@ -1926,7 +1972,8 @@ __global__ __launch_bounds__(64) void k_vm_signg(uint32_t n, VmDev p0, VmDev p1,
     if (active)
       for (uint32_t q = lane; q < 96; q += W) slot_put(slots, VM_SIGNG1_IN[q], hst + q * 12);
     __syncthreads();
-    vm::run(p1.code, VM_SIGNG1_NPHASES, W, lane, active, slots, cst, signg_scalar(d, r), vm::Out{nullptr, 0, 0});
+    vm::run<false, false>(p1.code, VM_SIGNG1_NPHASES, W, lane, active, slots, cst, signg_scalar(d, r),
+                          vm::Out{nullptr, 0, 0});
     __syncthreads();
     if (active && lane < 6)
       for (int l = 0; l < 12; ++l) hst[lane * 12 + l] = slots[VM_SIGNG1_OUT[lane] * 12 + l];
@@ -1992,7 +2039,8 @@ __global__ __launch_bounds__(64) void k_vm_pkchk(uint32_t n, VmDev prog, const u
     hdr[0] = bad | inf << 1 | xz << 2;
   }
   __syncthreads();
-  vm::run(prog.code, VM_PKCHK_NPHASES, VM_PKCHK_W, lane, active, slots, cst, 0, vm::Out{nullptr, 0, 0});
+  VM_ASSERT_NO_INV(PKCHK);
+  vm::run<false, false>(prog.code, VM_PKCHK_NPHASES, VM_PKCHK_W, lane, active, slots, cst, 0, vm::Out{nullptr, 0, 0});
   __syncthreads();
   if (!active) return;
   const uint32_t pf = hdr[0];
@@ -2041,7 +2089,7 @@ __global__ __launch_bounds__(64) void k_vm_g1tree(uint32_t m, VmDev prog, uint32
     }
   }
   __syncthreads();
-  vm::run(prog.code, prog.nphases, W, lane, active, slots, cst, 0, vm::Out{nullptr, 0, 0});
+  vm::run<false, false>(prog.code, prog.nphases, W, lane, active, slots, cst, 0, vm::Out{nullptr, 0, 0});
   if (active) {
     for (uint32_t k = lane; k < 3; k += W) {
       Fp v;
@@ -2087,7 +2135,8 @@ __global__ __launch_bounds__(64) void k_vm_g1grp(VmDev prog, const uint32_t* __r
     slot_put(slots, VM_G1GRP_IN[lane], v.v);
   }
   __syncthreads();
-  vm::run(prog.code, VM_G1GRP_NPHASES, VM_G1GRP_W, lane, active, slots, cst, 0, vm::Out{nullptr, 0, 0});
+  VM_ASSERT_NO_INV(G1GRP);
+  vm::run<false, false>(prog.code, VM_G1GRP_NPHASES, VM_G1GRP_W, lane, active, slots, cst, 0, vm::Out{nullptr, 0, 0});
   if (active && lane == 0 && !(flags[0] & PKF_INF) && !slot_flag_get(slots, VM_G1GRP_OUT[VM_G1GRP_OUT_PK_GRP]))
     flags[0] |= PKF_GRP;
 }
@@ -2302,7 +2351,8 @@ __global__ __launch_bounds__(64) void k_vm_pkdec(uint32_t n, VmDev prog, const u
     hdr[0] = bad | inf << 1 | xz << 2;
   }
   __syncthreads();
-  vm::run(prog.code, VM_PKDEC_NPHASES, W, lane, active, slots, cst, 0, vm::Out{nullptr, 0, 0});
+  VM_ASSERT_NO_INV(PKDEC);
+  vm::run<false, false>(prog.code, VM_PKDEC_NPHASES, W, lane, active, slots, cst, 0, vm::Out{nullptr, 0, 0});
   if (active && lane == 0) {
     const uint32_t pf = hdr[0];
     int32_t c = BLST_SUCCESS;

@@ -132,6 +132,9 @@ def emit(consts, built, path):
         lines.append("#define VM_%s_NSCR %d" % (N, getattr(sc, "nscr", 0)))
         lines.append("#define VM_%s_NIN %d" % (N, len(ins)))
         lines.append("#define VM_%s_NOUT %d" % (N, len(outs)))
+        # whether the program runs an inversion: the kernels of programs without one bind an
+        # interpreter without the inversion's code (fpvm.hpp run<SIDE, INV>)
+        lines.append("#define VM_%s_HAS_INV %d" % (N, int(any(op.kind == "inv" for op in prog.ops))))
         slot_in = [sc.slot_of.get(prog.inputs[n], 0xFFFF) for n in ins]
         slot_out = [sc.slot_of[prog.outputs[n]] for n in outs]
         st = {prog.ops[v].name: prog.ops[v].imm for n, v in prog.outputs.items() if prog.ops[v].kind == "st"}

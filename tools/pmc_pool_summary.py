@@ -39,8 +39,10 @@ def product_phases():
     return json.loads(m.group(1))
 
 
-def main(tag):
+def main(tag, icache_name=None):
     base = os.path.join(ROOT, "gpurun_out", tag, "pmcpool")
+    if icache_name:
+        return icache(base, tag, icache_name)
     a, na = pool_totals(os.path.join(base, "a", "*counter_collection.csv"))
     b, nb = pool_totals(os.path.join(base, "b", "*counter_collection.csv"))
     f, _ = pool_totals(os.path.join(base, "fetch", "*counter_collection.csv"))
@@ -82,5 +84,40 @@ def main(tag):
     print(json.dumps({k: v for k, v in doc.items() if k not in ("schedule", "per_quad")}))
 
 
+def icache(base, tag, name):
+    """Passes c and d of tools/pmc_pool.sh (instruction fetch, instruction cache) under `base`
+    (the tag's pass directory, main) -> profiles/<name>.json. The SQ wait counters are in
+    quad-cycles like SQ_WAVE_CYCLES, so their ratios are shares of the waves' resident time; the
+    SQC counters are summed over the instruction caches (one per CU pair)."""
+    c, nc = pool_totals(os.path.join(base, "c", "*counter_collection.csv"))
+    d, _ = pool_totals(os.path.join(base, "d", "*counter_collection.csv"))
+    quads = BATCHES * QUADS_PER_BATCH
+
+    def ratio(t, num, den):
+        return round(t[num] / t[den], 5) if t.get(den) else None
+
+    doc = {
+        "source": "rocprofv3 --pmc passes c and d (tools/pmc_pool.sh) over tools/pool_probe.py 4096 6 2, %s build; "
+                  "totals over the pool's dispatches / %d quads. rocprofv3 serialises dispatches: the pool runs "
+                  "alone, without the final-stream kernels that share its CUs in a pipelined run" % (tag, quads),
+        "dispatches": nc,
+        "quads": quads,
+        "per_quad": {k: round(v / quads, 1) for k, v in sorted({**c, **d}.items()) if k != "SQ_WAVES"},
+        "wait_any_share": ratio(c, "SQ_WAIT_ANY", "SQ_WAVE_CYCLES"),
+        "wait_inst_any_share": ratio(c, "SQ_WAIT_INST_ANY", "SQ_WAVE_CYCLES"),
+        "ifetch_level_mean": ratio(c, "SQ_IFETCH_LEVEL", "SQ_BUSY_CYCLES"),
+        "icache_miss_share": ratio(d, "SQC_ICACHE_MISSES", "SQC_ICACHE_REQ"),
+        "icache_miss_dup_share": ratio(d, "SQC_ICACHE_MISSES_DUPLICATE", "SQC_ICACHE_REQ"),
+        "icache_hit_share": ratio(d, "SQC_ICACHE_HITS", "SQC_ICACHE_REQ"),
+        "tc_inst_req_per_icache_req": ratio(d, "SQC_TC_INST_REQ", "SQC_ICACHE_REQ"),
+    }
+    with open(os.path.join(ROOT, "profiles", "%s.json" % name), "w") as fh:
+        json.dump(doc, fh, indent=1)
+    print(json.dumps({k: v for k, v in doc.items() if k != "per_quad"}))
+
+
 if __name__ == "__main__":
-    main(sys.argv[1])
+    if len(sys.argv) > 3 and sys.argv[2] == "icache":
+        main(sys.argv[1], sys.argv[3])
+    else:
+        main(sys.argv[1])

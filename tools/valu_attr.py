@@ -12,7 +12,8 @@ Two inputs:
     words (spills of the phase, fills of the next phase, whose loads the phase issues);
   * how many VALU instructions one pass of each path issues: counted in the gfx950 ISA of
     k_vm_pool's vote loop (hipcc --cuda-device-only -S of csrc/ovhip.hip, the blocks of
-    vote_quad<false>'s vm::run<true>), one table per build below.
+    vote_quad's vm::run<true, ...>; until the shared loop, vote_quad<false>'s), one table per
+    build below.
 The product of the two, summed, is the static VALU count per vote program run = per quad (one
 wave runs the four slices); tools/pmc_pool_summary.py's SQ_INSTS_VALU per quad measures the same
 quantity on the GPU (r05ad: 1.258 M), which pins the table.
@@ -104,6 +105,15 @@ PATHS = {
 PATHS["r06x"] = dict(PATHS["r06"])
 PATHS["r06x"]["lin_sum with negations, D only (r06x)"] = (70, "lin")
 PATHS["r06x"]["lin_sum with negations, C and D (r06x)"] = (82, "lin")
+# shared: one vote loop for vote and vote_t, exec without the inversion.
+# The pool keeps the loop unrolled three times over its register rings, so the per-path blocks are
+# r06x's (the inversion sat behind a per-lane branch no vote phase takes); what changes is the
+# loop row: no ring copies, one add + compare per phase. A one-copy build (OVH_POOL_UNROLL=1)
+# pays 6 moves per phase instead ("shared1").
+PATHS["shared"] = dict(PATHS["r06x"])
+PATHS["shared"]["loop: prefetch ring rotation + loop test"] = (0, "ring")
+PATHS["shared1"] = dict(PATHS["r06x"])
+PATHS["shared1"]["loop: prefetch ring rotation + loop test"] = (6, "ring")
 
 
 def load_prog(inc, name="VOTE"):
@@ -170,7 +180,7 @@ def phase_counts(w, nph, code, side):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--inc", default=os.path.join(ROOT, "consensus_overlord_amd", "csrc", "vm_progs.inc"))
-    ap.add_argument("--build", default=max(PATHS))
+    ap.add_argument("--build", default="shared", choices=sorted(PATHS))
     ap.add_argument("--md", action="store_true")
     a = ap.parse_args()
     w, nph, code, side = load_prog(a.inc)
