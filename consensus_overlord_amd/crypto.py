@@ -230,6 +230,27 @@ class ConsensusCrypto:
         raise_for(self.lib.ovh_vote_digests(self.ctx.ptr, n, ptr(h), ptr(r), ptr(t), ptr(bh), ptr(lens), ptr(out)))
         return [out[i].tobytes() for i in range(n)]
 
+    @staticmethod
+    def _packed(items):
+        """Byte strings -> (one concatenated uint8 array, uint64 offsets[n + 1])."""
+        items = [bytes(x) for x in items]
+        off = np.zeros(len(items) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum(np.array([len(x) for x in items], dtype=np.uint64))
+        data = np.frombuffer(b"".join(items) or b"\0", dtype=np.uint8)
+        return data, off
+
+    def hash_batch(self, msgs: Sequence[bytes]) -> List[bytes]:
+        """Crypto::hash of many messages on the device (ovh_sm3_batch: one lane per message),
+        element i == hash(msgs[i])."""
+        n = len(msgs)
+        if n == 0:
+            return []
+        data, off = self._packed(msgs)
+        out = np.zeros((n, 32), dtype=np.uint8)
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+        raise_for(self.lib.ovh_sm3_batch(self.ctx.ptr, n, ptr(data), ptr(off), ptr(out)))
+        return [out[i].tobytes() for i in range(n)]
+
     def aggregate_public_keys(self, voters: Sequence[bytes]) -> bytes:
         """BlsPublicKey::aggregate (consensus.rs:371) -> 48-byte compressed."""
         vd, vl = _concat(voters)
@@ -378,6 +399,27 @@ class ConsensusCrypto:
         except ConsensusError:
             return False
         return True
+
+    def check_block_batch(self, blocks):
+        """check_block for many blocks in one device pass (ovh_check_blocks) against the validator
+        table (update_pubkeys): blocks = (proposal_height, proposal_data, proof) tuples ->
+        (ok bool[n], reasons int32[n]); ok[j] == check_block(*blocks[j]), reasons[j] is 0 or why
+        not: 300 the proof does not decode, 301 height or block hash differ, else the
+        verify_aggregated_signature code of the QC. The proposal hashes (SM3), the proof decoding
+        and the QC batch all run inside the library, behind one host synchronisation;
+        check_blocks below is the same composed in Python."""
+        n = len(blocks)
+        if n == 0:
+            return np.zeros(0, dtype=bool), np.zeros(0, dtype=np.int32)
+        heights = np.array([b[0] for b in blocks], dtype=np.uint64)
+        data, data_off = self._packed([b[1] for b in blocks])
+        proofs, proof_off = self._packed([b[2] for b in blocks])
+        ok = np.zeros(n, dtype=np.uint8)
+        reasons = np.zeros(n, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+        raise_for(self.lib.ovh_check_blocks(self.ctx.ptr, n, ptr(heights), ptr(data), ptr(data_off), ptr(proofs),
+                                            ptr(proof_off), ptr(ok), ptr(reasons)))
+        return ok.astype(bool), reasons
 
     def check_blocks(self, blocks) -> np.ndarray:
         """Many check_block calls against the validator table (update_pubkeys) in one pass:

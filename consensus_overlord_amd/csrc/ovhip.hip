@@ -19,6 +19,10 @@
 //   k_vm_rs       per vote r_i sigma_i (the MSM's terms), then fold levels 0-1 of (f, r sigma)
 //   k_vm_group    the same check per 16-vote group
 //   k_vm_votechk  per vote of a failing group: f_i * Miller(-G1, r_i sigma_i) == 1
+// Block sync (ovh_check_blocks), DESIGN.md section 3.5:
+//   k_sm3_bulk    lane per message: SM3 of the proposal bytes (sm3_bulk.hpp; also ovh_sm3_batch*)
+//   k_cb_gate     digest == the proof's block hash ? the flag stays on the device
+//   k_vote_digest, k_qc_apk, the verify batch over the QCs, then k_cb_finish: ok / reasons
 // Per-vote state lives in HBM as structure-of-arrays by limb: limb k of element i of an Fp
 // plane j at slab[(j * 12 + k) * cap + i].
 #include <hip/hip_runtime.h>
@@ -42,8 +46,10 @@
 #include "bls/verify.hpp"
 #include "fpvm.hpp"
 #include "keygen.hpp"
+#include "proof.hpp"
 #include "rlp.hpp"
 #include "sm3.hpp"
+#include "sm3_bulk.hpp"
 #ifdef OVH_VM_PROGS
 #include OVH_VM_PROGS  // A/B builds: another generation of the programs
 #else
@@ -5341,52 +5347,88 @@ int ovh_msg_cache_stats(ovh_ctx* c, uint64_t stats[2]) {
   return 0;
 }
 
+// The voters of one QC (extract_voters: bit k MSB-first <-> k-th key in sorted order; the zip
+// truncates, bits past the list are ignored), appended to ent as table entries. The bitmap length
+// is the QC's own. Returns how the QC is decided -- consensus.rs:454-458 (key parse) -> :371
+// (empty aggregate) -> ...: OVH_ERR_PUBKEY, BLST_AGGR_TYPE_MISMATCH, QC_SINGLE (a key outside G1:
+// the sum's own group check decides, the single-QC path, k_vm_g1grp) or 0 (the device batch).
+#define QC_SINGLE (-1)
+static int qc_voters(const ValidatorTable& t, const uint8_t* bm, size_t bitmap_len, std::vector<uint32_t>& ent) {
+  const size_t nbits = bitmap_len * 8 < t.n ? bitmap_len * 8 : t.n;
+  uint32_t fl = 0, cnt = 0;
+  for (size_t k = 0; k < nbits; ++k)
+    if ((bm[k / 8] >> (7 - k % 8)) & 1) {
+      const uint32_t e = t.sorted[k];
+      ent.push_back(e);
+      fl |= t.hflags[e];
+      ++cnt;
+    }
+  if (fl & PKF_PARSE) return OVH_ERR_PUBKEY;
+  if (!cnt) return BLST_AGGR_TYPE_MISMATCH;
+  if (fl & PKF_GRP) return QC_SINGLE;
+  return 0;
+}
+
+// One QC on the per-call path (verify_aggregated_locked: any signature length, any keys) over the
+// table entries ent[0 .. cnt). Synchronous.
+static int qc_single_locked(ovh_ctx* c, const uint32_t* ent, size_t cnt, const uint8_t* sig, size_t sig_len,
+                            const uint8_t* hash) {
+  const ValidatorTable& t = c->tab;
+  std::vector<uint8_t> cat;
+  std::vector<size_t> lens;
+  for (size_t k = 0; k < cnt; ++k) {
+    cat.insert(cat.end(), t.keys[ent[k]].begin(), t.keys[ent[k]].end());
+    lens.push_back(48);
+  }
+  return verify_aggregated_locked(c, sig, sig_len, hash, 32, cat.data(), lens.data(), cnt);
+}
+
+// The device batch of nd >= 1 QCs, everything device-resident: apk per QC (the entries
+// dent[doff[j] .. doff[j + 1]) of the table) -> vote_t over (sig, hash, apk), codes to dc. Nothing
+// waits; *st is the stream the codes are complete on.
+static int qc_device_batch(ovh_ctx* c, size_t nd, const uint8_t* d_sigs, const uint8_t* d_hashes, const uint32_t* doff,
+                           const uint32_t* dent, int32_t* dc, hipStream_t* st) {
+  const ValidatorTable& t = c->tab;
+  uint32_t* qflags = c->qc_buf + (size_t)3 * 12 * c->qc_cap;
+  k_qc_apk<<<(uint32_t)nd, 64, 0, c->stream>>>((uint32_t)nd, doff, dent, Slab{t.planes, t.cap},
+                                          Slab{c->qc_buf, c->qc_cap}, qflags);
+  HIPCHK(hipGetLastError());
+  const KeySrc qk{nullptr, PkSrc{c->qc_buf, c->qc_cap, qflags, nullptr}};
+  if (nd == 1) {
+    CHK(verify_one_locked(c, d_sigs, d_hashes, qk, dc));
+    *st = c->stream;
+  } else {
+    CHK(verify_async_locked(c, nd, d_sigs, d_hashes, qk, dc));
+    *st = c->fs[c->last_slot];
+  }
+  return 0;
+}
+
 static int qc_batch_locked(ovh_ctx* c, size_t nq, const uint8_t* sigs, const uint8_t* hashes, const uint8_t* bitmaps,
                            size_t bitmap_len, int32_t* codes) {
   HIPCHK(hipSetDevice(c->device));
   const ValidatorTable& t = c->tab;
-  // voters per QC (extract_voters: bit k MSB-first <-> k-th key in sorted order; zip truncates)
-  const size_t nbits = bitmap_len * 8 < t.n ? bitmap_len * 8 : t.n;
   std::vector<uint32_t> off(1, 0), ent;
   std::vector<size_t> dev;  // QCs that go to the device batch
   for (size_t q = 0; q < nq; ++q) {
-    const uint8_t* bm = bitmaps + q * bitmap_len;
-    uint32_t fl = 0, cnt = 0;
     const size_t start = ent.size();
-    for (size_t k = 0; k < nbits; ++k)
-      if ((bm[k / 8] >> (7 - k % 8)) & 1) {
-        const uint32_t e = t.sorted[k];
-        ent.push_back(e);
-        fl |= t.hflags[e];
-        ++cnt;
-      }
-    // consensus.rs:454-458 (key parse) -> :371 (empty aggregate) -> ...
-    if (fl & PKF_PARSE) {
-      codes[q] = OVH_ERR_PUBKEY;
-      ent.resize(start);
-    } else if (!cnt) {
-      codes[q] = BLST_AGGR_TYPE_MISMATCH;
-    } else if (fl & PKF_GRP) {
-      // a key outside G1: the sum's own group check decides -> the single-QC path (k_vm_g1grp)
-      std::vector<uint8_t> cat;
-      std::vector<size_t> lens;
-      for (size_t k = start; k < ent.size(); ++k) {
-        cat.insert(cat.end(), t.keys[ent[k]].begin(), t.keys[ent[k]].end());
-        lens.push_back(48);
-      }
-      ent.resize(start);
-      const int r =
-          verify_aggregated_locked(c, sigs + 96 * q, 96, hashes + 32 * q, 32, cat.data(), lens.data(), cnt);
+    const int k = qc_voters(t, bitmaps + q * bitmap_len, bitmap_len, ent);
+    if (k == 0) {
+      dev.push_back(q);
+      off.push_back((uint32_t)ent.size());
+      continue;
+    }
+    if (k == QC_SINGLE) {
+      const int r = qc_single_locked(c, ent.data() + start, ent.size() - start, sigs + 96 * q, 96, hashes + 32 * q);
       if (r >= OVH_ERR_ARG) return r;
       codes[q] = r;
     } else {
-      dev.push_back(q);
-      off.push_back((uint32_t)ent.size());
+      codes[q] = k;
     }
+    ent.resize(start);
   }
   const size_t nd = dev.size();
   if (!nd) return 0;
-  // device batch: apk per QC -> vote_t over (sig, hash, apk)
   CHK(ensure_qc_buf(c, nd));
   const size_t bytes = nd * (96 + 32 + 4) + off.size() * 4 + ent.size() * 4 + 256;
   CHK(ensure_in(c, bytes));
@@ -5403,13 +5445,8 @@ static int qc_batch_locked(ovh_ctx* c, size_t nq, const uint8_t* sigs, const uin
   HIPCHK(hipMemcpyAsync(d + nd * 96, hh.data(), nd * 32, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(doff, off.data(), off.size() * 4, hipMemcpyHostToDevice, c->stream));
   if (!ent.empty()) HIPCHK(hipMemcpyAsync(dent, ent.data(), ent.size() * 4, hipMemcpyHostToDevice, c->stream));
-  uint32_t* qflags = c->qc_buf + (size_t)3 * 12 * c->qc_cap;
-  k_qc_apk<<<(uint32_t)nd, 64, 0, c->stream>>>((uint32_t)nd, doff, dent, Slab{t.planes, t.cap},
-                                          Slab{c->qc_buf, c->qc_cap}, qflags);
-  HIPCHK(hipGetLastError());
-  const KeySrc qk{nullptr, PkSrc{c->qc_buf, c->qc_cap, qflags, nullptr}};
-  if (nd == 1) CHK(verify_one_locked(c, d, d + 96, qk, dc));
-  else CHK(verify_async_locked(c, nd, d, d + nd * 96, qk, dc));
+  hipStream_t st;
+  CHK(qc_device_batch(c, nd, d, d + nd * 96, doff, dent, dc, &st));
   CHK(sync_all(c));
   std::vector<int32_t> dcodes(nd);
   HIPCHK(hipMemcpyAsync(dcodes.data(), dc, 4 * nd, hipMemcpyDeviceToHost, c->stream));
@@ -5427,6 +5464,258 @@ int ovh_verify_qc_batch(ovh_ctx* c, size_t nq, const uint8_t* sigs, const uint8_
   std::lock_guard<std::mutex> g(s->mu);
   if (!s->tab.n) return OVH_ERR_ARG;
   return qc_batch_locked(s, nq, sigs, hashes, bitmaps, bitmap_len, codes);
+}
+
+// ------------------------------------------------------------------------ ovh_check_blocks
+// The gate of check_block (consensus.rs:165): flag j = 1 when SM3(proposal data j) differs from
+// proof j's block hash. The flag stays on the device; k_cb_finish reads it.
+__global__ __launch_bounds__(WG) void k_cb_gate(uint32_t n, const uint8_t* __restrict__ dig,
+                                                const uint8_t* __restrict__ pbh, uint32_t* __restrict__ flag) {
+  const uint32_t i = blockIdx.x * WG + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t* a = (const uint32_t*)(dig + (size_t)i * 32);
+  const uint32_t* b = (const uint32_t*)(pbh + (size_t)i * 32);
+  uint32_t d = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) d |= a[k] ^ b[k];
+  flag[i] = d != 0;
+}
+
+// The verdicts, with the reference's precedence: what the host decided for good (CB_FINAL: an
+// undecodable proof, a height or hash-length mismatch, a block that went the per-call way), then
+// the gate's flag, then the voters' code the host found (no voter, a key that does not parse) or
+// the code of the block's QC in the verify batch.
+#define CB_FINAL 0x10000
+__global__ __launch_bounds__(WG) void k_cb_finish(uint32_t n, const uint32_t* __restrict__ flag,
+                                                  const int32_t* __restrict__ pre, const int32_t* __restrict__ qi,
+                                                  const int32_t* __restrict__ codes, int32_t* __restrict__ reasons,
+                                                  uint8_t* __restrict__ ok) {
+  const uint32_t i = blockIdx.x * WG + threadIdx.x;
+  if (i >= n) return;
+  const int32_t p = pre[i];
+  int32_t r;
+  if (p & CB_FINAL) r = p & 0xffff;
+  else if (flag[i]) r = OVH_CB_MISMATCH;
+  else r = qi[i] >= 0 ? codes[qi[i]] : p;
+  reasons[i] = r;
+  ok[i] = r == 0;
+}
+
+// Messages ordered by block count, longest first, so the 64 lanes of a k_sm3_bulk wave run
+// similar lengths; empty when the counts are all equal (no order needed).
+static void sm3_order(size_t n, const uint64_t* off, std::vector<uint32_t>& order) {
+  order.clear();
+  bool same = true;
+  const uint64_t b0 = (off[1] - off[0] + 72) >> 6;
+  for (size_t i = 1; i < n && same; ++i) same = ((off[i + 1] - off[i] + 72) >> 6) == b0;
+  if (same) return;
+  order.resize(n);
+  for (size_t i = 0; i < n; ++i) order[i] = (uint32_t)i;
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+    return ((off[a + 1] - off[a] + 72) >> 6) > ((off[b + 1] - off[b] + 72) >> 6);
+  });
+}
+
+// offsets of n items: monotonic, at most 2^32 - 1 bytes in all
+static bool offsets_ok(size_t n, const uint64_t* off) {
+  for (size_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i]) return false;
+  return off[n] - off[0] <= 0xFFFFFFFFull;
+}
+
+// check_block for n blocks on one device, one host synchronisation.
+// Host: the proofs decoded (proof.hpp), the height check, the voters of each bitmap; blocks the
+// batch cannot take (a signature that is not 96 bytes, a selected key outside G1) are answered
+// per call first. Device: the proposal bytes -> k_sm3_bulk -> k_cb_gate; the vote digests of the
+// QCs -> k_qc_apk -> the verify batch on device-resident hashes; k_cb_finish on the batch's last
+// stream. A block whose hash mismatches still rides in the batch (only the device knows) and its
+// verdict is gated by the flag. Caller holds c->mu.
+static int check_blocks_locked(ovh_ctx* c, size_t n, const uint64_t* heights, const uint8_t* data,
+                               const uint64_t* data_off, const uint8_t* proofs, const uint64_t* proof_off, uint8_t* ok,
+                               int32_t* reasons) {
+  HIPCHK(hipSetDevice(c->device));
+  const ValidatorTable& t = c->tab;
+  std::vector<int32_t> pre(n), qi(n, -1);
+  std::vector<uint8_t> pbh(n * 32, 0);
+  std::vector<uint32_t> qoff(1, 0), ent;
+  std::vector<size_t> dev;  // blocks whose QC goes to the device batch
+  std::vector<ProofView> pv(n);
+  for (size_t j = 0; j < n; ++j) {
+    ProofView& v = pv[j];
+    if (!decode_proof(proofs + proof_off[j], (size_t)(proof_off[j + 1] - proof_off[j]), &v)) {
+      pre[j] = CB_FINAL | OVH_CB_PROOF_DECODE;
+      continue;
+    }
+    // a block hash that is not 32 bytes cannot equal an SM3 output
+    if (v.height != heights[j] || v.hash_len != 32) {
+      pre[j] = CB_FINAL | OVH_CB_MISMATCH;
+      continue;
+    }
+    memcpy(&pbh[32 * j], v.block_hash, 32);
+    const size_t start = ent.size();
+    const int k = qc_voters(t, v.bitmap, v.bitmap_len, ent);
+    if (v.sig_len == 96 && k == 0) {
+      qi[j] = (int32_t)dev.size();
+      dev.push_back(j);
+      qoff.push_back((uint32_t)ent.size());
+      continue;
+    }
+    if (v.sig_len == 96 && k != QC_SINGLE) {  // no voter / a key that does not parse: behind the gate
+      pre[j] = k;
+      ent.resize(start);
+      continue;
+    }
+    // the per-call path, as a single check_block: host SM3, then verify_aggregated
+    uint8_t h[32];
+    sm3_digest(data + data_off[j], (size_t)(data_off[j + 1] - data_off[j]), h);
+    int r = OVH_CB_MISMATCH;
+    if (!memcmp(h, v.block_hash, 32)) {
+      if (v.sig_len > 4096) {
+        r = BLST_BAD_ENCODING;  // no signature encoding is that long (ovh_verify_aggregated's limit)
+      } else {
+        vote_digest(h, v.height, v.round, 1 /* Precommit */, v.block_hash, 32);
+        r = qc_single_locked(c, ent.data() + start, ent.size() - start, v.sig, v.sig_len, h);
+        if (r >= OVH_ERR_ARG) return r;
+      }
+    }
+    pre[j] = CB_FINAL | r;
+    ent.resize(start);
+  }
+  const size_t nd = dev.size();
+  const uint64_t base = data_off[0], total = data_off[n] - base;
+  std::vector<uint32_t> order;
+  sm3_order(n, data_off, order);
+  // staging: one host image of everything but the proposal bytes, copied in one piece
+  size_t pos = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = pos;
+    pos = (pos + bytes + 255) / 256 * 256;
+    return o;
+  };
+  const size_t o_off = take(8 * (n + 1)), o_pbh = take(32 * n), o_pre = take(4 * n), o_qi = take(4 * n),
+               o_ord = take(4 * order.size()), o_vh = take(8 * nd), o_vr = take(8 * nd), o_vt = take(nd),
+               o_vl = take(nd), o_vb = take((size_t)VOTE_HASH_MAX * nd), o_sig = take(96 * nd),
+               o_qoff = take(4 * qoff.size()), o_ent = take(4 * ent.size());
+  const size_t image = pos;
+  const size_t o_dig = take(32 * n), o_flag = take(4 * n), o_hash = take(32 * nd), o_dc = take(4 * nd),
+               o_out = take(5 * n), o_data = take((size_t)total + 4);
+  if (nd) CHK(ensure_qc_buf(c, nd));
+  CHK(ensure_in(c, pos));
+  uint8_t* d = c->in_buf;
+  std::vector<uint8_t> hm(image, 0), out(5 * n);
+  {
+    uint64_t* p = (uint64_t*)&hm[o_off];
+    for (size_t j = 0; j <= n; ++j) p[j] = data_off[j] - base;
+    memcpy(&hm[o_pbh], pbh.data(), 32 * n);
+    memcpy(&hm[o_pre], pre.data(), 4 * n);
+    memcpy(&hm[o_qi], qi.data(), 4 * n);
+    if (!order.empty()) memcpy(&hm[o_ord], order.data(), 4 * n);
+    uint64_t* vh = (uint64_t*)&hm[o_vh];
+    uint64_t* vr = (uint64_t*)&hm[o_vr];
+    for (size_t q = 0; q < nd; ++q) {
+      const ProofView& v = pv[dev[q]];
+      vh[q] = v.height;
+      vr[q] = v.round;
+      hm[o_vt + q] = 1;  // Precommit
+      hm[o_vl + q] = 32;
+      memcpy(&hm[o_vb + (size_t)VOTE_HASH_MAX * q], v.block_hash, 32);
+      memcpy(&hm[o_sig + 96 * q], v.sig, 96);
+    }
+    memcpy(&hm[o_qoff], qoff.data(), 4 * qoff.size());
+    if (!ent.empty()) memcpy(&hm[o_ent], ent.data(), 4 * ent.size());
+  }
+  // an error return drains the streams that copy from / into the host buffers above before they
+  // die; the normal return has waited already (the call's one synchronisation)
+  struct Drain {
+    hipStream_t s[2];
+    bool armed;
+    ~Drain() {
+      if (armed)
+        for (hipStream_t x : s)
+          if (x) (void)hipStreamSynchronize(x);
+    }
+  } drain{{c->stream, nullptr}, true};
+  HIPCHK(hipMemcpyAsync(d, hm.data(), image, hipMemcpyHostToDevice, c->stream));
+  if (total) HIPCHK(hipMemcpyAsync(d + o_data, data + base, (size_t)total, hipMemcpyHostToDevice, c->stream));
+  k_sm3_bulk<<<nblk(n), WG, 0, c->stream>>>((uint32_t)n, d + o_data, (const uint64_t*)(d + o_off),
+                                            order.empty() ? nullptr : (const uint32_t*)(d + o_ord), d + o_dig);
+  k_cb_gate<<<nblk(n), WG, 0, c->stream>>>((uint32_t)n, d + o_dig, d + o_pbh, (uint32_t*)(d + o_flag));
+  HIPCHK(hipGetLastError());
+  hipStream_t st = c->stream;
+  if (nd) {
+    k_vote_digest<<<nblk(nd), WG, 0, c->stream>>>((uint32_t)nd, (const uint64_t*)(d + o_vh), (const uint64_t*)(d + o_vr),
+                                                  d + o_vt, d + o_vb, d + o_vl, d + o_hash);
+    HIPCHK(hipGetLastError());
+    CHK(qc_device_batch(c, nd, d + o_sig, d + o_hash, (const uint32_t*)(d + o_qoff), (const uint32_t*)(d + o_ent),
+                        (int32_t*)(d + o_dc), &st));
+  }
+  k_cb_finish<<<nblk(n), WG, 0, st>>>((uint32_t)n, (const uint32_t*)(d + o_flag), (const int32_t*)(d + o_pre),
+                                      (const int32_t*)(d + o_qi), (const int32_t*)(d + o_dc), (int32_t*)(d + o_out),
+                                      d + o_out + 4 * n);
+  HIPCHK(hipGetLastError());
+  drain.s[1] = st;
+  HIPCHK(hipMemcpyAsync(out.data(), d + o_out, 5 * n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  drain.armed = false;
+  CHK(pool_failed(c));
+  memcpy(ok, &out[4 * n], n);
+  if (reasons) memcpy(reasons, out.data(), 4 * n);
+  return 0;
+}
+
+int ovh_check_blocks(ovh_ctx* c, size_t n, const uint64_t* heights, const uint8_t* data, const uint64_t* data_off,
+                     const uint8_t* proofs, const uint64_t* proof_off, uint8_t* ok, int32_t* reasons) {
+  if (!c || (n && (!heights || !data || !data_off || !proofs || !proof_off || !ok))) return OVH_ERR_ARG;
+  if (n == 0) return 0;
+  if (n > (1u << 20) || !offsets_ok(n, data_off) || !offsets_ok(n, proof_off)) return OVH_ERR_ARG;
+  ovh_ctx* s = c->sub.empty() ? c : c->sub[0];
+  std::lock_guard<std::mutex> g(s->mu);
+  return check_blocks_locked(s, n, heights, data, data_off, proofs, proof_off, ok, reasons);
+}
+
+int ovh_sm3_batch_device(ovh_ctx* c, size_t n, const uint8_t* d_data, const uint64_t* d_off, uint8_t* d_digests) {
+  if (!c || n > (1u << 24) || (n && (!d_data || !d_off || !d_digests))) return OVH_ERR_ARG;
+  if (n == 0) return 0;
+  ovh_ctx* s = c->sub.empty() ? c : c->sub[0];
+  std::lock_guard<std::mutex> g(s->mu);
+  HIPCHK(hipSetDevice(s->device));
+  k_sm3_bulk<<<nblk(n), WG, 0, s->stream>>>((uint32_t)n, d_data, d_off, nullptr, d_digests);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ovh_sm3_batch(ovh_ctx* c, size_t n, const uint8_t* data, const uint64_t* off, uint8_t* digests) {
+  if (!c || n > (1u << 24) || (n && (!off || !digests))) return OVH_ERR_ARG;
+  if (n == 0) return 0;
+  if (!offsets_ok(n, off)) return OVH_ERR_ARG;
+  const uint64_t base = off[0], total = off[n] - base;
+  if (total && !data) return OVH_ERR_ARG;
+  std::vector<uint32_t> order;
+  sm3_order(n, off, order);
+  std::vector<uint64_t> rel(n + 1);
+  for (size_t i = 0; i <= n; ++i) rel[i] = off[i] - base;
+  ovh_ctx* s = c->sub.empty() ? c : c->sub[0];
+  std::lock_guard<std::mutex> g(s->mu);
+  HIPCHK(hipSetDevice(s->device));
+  // staging: offsets, order, digests, then the message bytes
+  const size_t o_ord = (8 * (n + 1) + 255) / 256 * 256, o_dig = (o_ord + 4 * n + 255) / 256 * 256,
+               o_data = o_dig + 32 * n;
+  CHK(ensure_in(s, o_data + (size_t)total + 4));
+  uint8_t* d = s->in_buf;
+  // the stream copies from the vectors above: an error return waits for it first
+  struct Drain {
+    hipStream_t s;
+    ~Drain() { (void)hipStreamSynchronize(s); }
+  } drain{s->stream};
+  HIPCHK(hipMemcpyAsync(d, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice, s->stream));
+  if (!order.empty()) HIPCHK(hipMemcpyAsync(d + o_ord, order.data(), 4 * n, hipMemcpyHostToDevice, s->stream));
+  if (total) HIPCHK(hipMemcpyAsync(d + o_data, data + base, (size_t)total, hipMemcpyHostToDevice, s->stream));
+  k_sm3_bulk<<<nblk(n), WG, 0, s->stream>>>((uint32_t)n, d + o_data, (const uint64_t*)d,
+                                            order.empty() ? nullptr : (const uint32_t*)(d + o_ord), d + o_dig);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(digests, d + o_dig, 32 * n, hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  return 0;
 }
 
 // ovh_build_qc on one device (caller holds c->mu, the table is set): the round's verify batch on

@@ -95,6 +95,17 @@ void* ovh_stream(ovh_ctx* ctx);
 
 /* Crypto::hash -> util.rs:83-87 sm3_hash. */
 int ovh_sm3(const uint8_t* msg, size_t len, uint8_t out[32]);
+/* Crypto::hash in bulk (util.rs:83-87): digest i = SM3(data[off[i] .. off[i+1])), i < n, on the
+ * device (one lane per message; csrc/sm3_bulk.hpp). Host form: host buffers, synchronous;
+ * OVH_ERR_ARG for a NULL pointer, n > 2^24, offsets that decrease or more than 2^32 - 1 bytes in
+ * all; n == 0 returns 0. _device: every pointer is device memory (d_data at any byte alignment),
+ * the kernel is enqueued on ovh_stream and the call returns without waiting (stream order), as
+ * ovh_vote_digests_device; an entry whose end offset is below its start gets the all-zero digest
+ * and nothing of it is read. The kernel reads aligned 32-bit words, so it may touch up to 3 bytes
+ * before the first and after the last byte of a message, inside the words that hold them. A
+ * multi-device context uses its first device. */
+int ovh_sm3_batch(ovh_ctx* ctx, size_t n, const uint8_t* data, const uint64_t* off /* n+1 */, uint8_t* digests /* n x 32 */);
+int ovh_sm3_batch_device(ovh_ctx* ctx, size_t n, const uint8_t* d_data, const uint64_t* d_off, uint8_t* d_digests);
 
 /* Vote digests on the device: digest i = SM3(rlp(Vote{height, round,
  * vote_type, block_hash})), the hash overlord signs and Consensus::check_block rebuilds
@@ -191,6 +202,31 @@ int ovh_msg_cache_stats(ovh_ctx* ctx, uint64_t stats[2]);
  * QCs. Needs ovh_set_validators. */
 int ovh_verify_qc_batch(ovh_ctx* ctx, size_t nq, const uint8_t* sigs, const uint8_t* hashes, const uint8_t* bitmaps,
                         size_t bitmap_len, int32_t* codes);
+
+/* Block sync in one device pass: Consensus::check_block (consensus.rs:143-207) for n blocks
+ * against the validator table (ovh_set_validators). Block j = proposal height heights[j], proposal
+ * data data[data_off[j] .. data_off[j+1]) and the overlord Proof's RLP bytes
+ * proofs[proof_off[j] .. proof_off[j+1]).
+ *   ok[j]       1 exactly when check_block(heights[j], data_j, proof_j) returns true, else 0.
+ *   reasons[j]  (may be NULL) 0 when ok[j] is 1, else, in the reference's order: OVH_CB_PROOF_DECODE
+ *               (Proof::decode failed, :158), OVH_CB_MISMATCH (proof.block_hash != sm3(data) or
+ *               proof.height != height, :165), then the ovh_verify_aggregated code of the QC over
+ *               hash(rlp(Vote{height, round, Precommit, block_hash})) and the voters of the bitmap
+ *               (1..7, 102; no bit set: 4). The bitmap length is each proof's own.
+ * The host decodes the proofs and expands the bitmaps; the device hashes the proposal bytes
+ * (SM3 in bulk), compares, builds the vote digests and the aggregated keys and checks every QC in
+ * one verify batch (secret coefficients, bisection: exact verdicts); the host waits once, after
+ * everything is enqueued. A proof whose signature is not 96 bytes, or that selects a key outside
+ * G1, is checked per call (ovh_verify_aggregated's path). Host buffers, synchronous,
+ * thread-safe; a multi-device context runs it on its first device. Returns 0 when the verdicts
+ * were written -- also with no validator table: every ok 0, as the reference with an empty
+ * authority list; OVH_ERR_ARG for a NULL pointer, offsets that decrease, n > 2^20 or more than
+ * 2^32 - 1 bytes of data or of proofs; device / RNG errors as elsewhere. */
+#define OVH_CB_PROOF_DECODE 300 /* Proof::decode failed (consensus.rs:158) */
+#define OVH_CB_MISMATCH 301     /* proof.block_hash != sm3(data) or proof.height != height (:165) */
+int ovh_check_blocks(ovh_ctx* ctx, size_t n, const uint64_t* heights, const uint8_t* data,
+                     const uint64_t* data_off /* n+1 */, const uint8_t* proofs, const uint64_t* proof_off /* n+1 */,
+                     uint8_t* ok /* n */, int32_t* reasons /* n, may be NULL */);
 
 /* The leader's side of a round in one device pass: verify the round's n votes on `hash` (the
  * SM3 of rlp(Vote), hash_len 32), select the votes that count, and aggregate their signatures

@@ -19,6 +19,9 @@ pub const OVH_ERR_PUBKEY: i32 = 102;
 pub const OVH_ERR_ARG: i32 = 103;
 pub const OVH_ERR_DEVICE: i32 = 200;
 pub const OVH_ERR_RNG: i32 = 201;
+/// `ovh_check_blocks` reasons beside the `ovh_verify_aggregated` codes.
+pub const OVH_CB_PROOF_DECODE: i32 = 300;
+pub const OVH_CB_MISMATCH: i32 = 301;
 
 pub const OVH_FLAG_AGG_NO_GROUPCHECK: u32 = 0x1;
 pub const OVH_FLAG_PROFILE: u32 = 0x2;
@@ -42,6 +45,9 @@ extern "C" {
     pub fn ovh_device_count(ctx: *mut OvhCtx) -> i32;
     pub fn ovh_stream(ctx: *mut OvhCtx) -> *mut c_void;
     pub fn ovh_sm3(msg: *const u8, len: usize, out: *mut u8) -> i32;
+    pub fn ovh_sm3_batch(ctx: *mut OvhCtx, n: usize, data: *const u8, off: *const u64, digests: *mut u8) -> i32;
+    pub fn ovh_sm3_batch_device(ctx: *mut OvhCtx, n: usize, d_data: *const u8, d_off: *const u64, d_digests: *mut u8) -> i32;
+    pub fn ovh_check_blocks(ctx: *mut OvhCtx, n: usize, heights: *const u64, data: *const u8, data_off: *const u64, proofs: *const u8, proof_off: *const u64, ok: *mut u8, reasons: *mut i32) -> i32;
     pub fn ovh_vote_digests_device(ctx: *mut OvhCtx, n: usize, heights: *const u64, rounds: *const u64, vote_types: *const u8, block_hashes: *const u8, hash_lens: *const u8, digests: *mut u8) -> i32;
     pub fn ovh_vote_digests(ctx: *mut OvhCtx, n: usize, heights: *const u64, rounds: *const u64, vote_types: *const u8, block_hashes: *const u8, hash_lens: *const u8, digests: *mut u8) -> i32;
     pub fn ovh_sk_parse(ctx: *mut OvhCtx, key: *const u8, key_len: usize, out_scalar: *mut u8) -> i32;

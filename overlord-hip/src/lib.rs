@@ -271,6 +271,48 @@ impl HipCrypto {
         })?;
         Ok((Bytes::copy_from_slice(&out), Bytes::from(bitmap), codes, taken))
     }
+
+    /// `Crypto::hash` of many messages on the device (`ovh_sm3_batch`: one lane per message),
+    /// digest i = SM3(msgs[i]). Blocking.
+    pub fn hash_batch(&self, msgs: &[Bytes]) -> Result<Vec<[u8; 32]>, Box<dyn Error + Send>> {
+        let mut off = Vec::with_capacity(msgs.len() + 1);
+        let mut data = Vec::with_capacity(msgs.iter().map(|m| m.len()).sum());
+        off.push(0u64);
+        for m in msgs {
+            data.extend_from_slice(m);
+            off.push(data.len() as u64);
+        }
+        let mut out = vec![[0u8; 32]; msgs.len()];
+        check(unsafe {
+            ffi::ovh_sm3_batch(self.raw(), msgs.len(), data.as_ptr(), off.as_ptr(), out.as_mut_ptr() as *mut u8)
+        })?;
+        Ok(out)
+    }
+
+    /// `Consensus::check_block` (consensus.rs:143-207) for many blocks in one device pass
+    /// (`ovh_check_blocks`) against the validator table of `update_pubkeys`: blocks are (proposal
+    /// height, proposal data, the overlord Proof's RLP bytes). Returns per block whether
+    /// check_block accepts it and, when not, why: OVH_CB_PROOF_DECODE, OVH_CB_MISMATCH or the
+    /// `verify_aggregated_signature` code of its QC. Blocking: call from `spawn_blocking`.
+    pub fn check_blocks(&self, blocks: &[(u64, Bytes, Bytes)]) -> Result<(Vec<bool>, Vec<i32>), Box<dyn Error + Send>> {
+        let n = blocks.len();
+        let heights: Vec<u64> = blocks.iter().map(|b| b.0).collect();
+        let (mut data, mut proofs) = (Vec::new(), Vec::new());
+        let (mut data_off, mut proof_off) = (vec![0u64], vec![0u64]);
+        for (_, d, p) in blocks {
+            data.extend_from_slice(d);
+            data_off.push(data.len() as u64);
+            proofs.extend_from_slice(p);
+            proof_off.push(proofs.len() as u64);
+        }
+        let mut ok = vec![0u8; n];
+        let mut reasons = vec![0i32; n];
+        check(unsafe {
+            ffi::ovh_check_blocks(self.raw(), n, heights.as_ptr(), data.as_ptr(), data_off.as_ptr(), proofs.as_ptr(),
+                                  proof_off.as_ptr(), ok.as_mut_ptr(), reasons.as_mut_ptr())
+        })?;
+        Ok((ok.into_iter().map(|b| b == 1).collect(), reasons))
+    }
 }
 
 impl OverlordCrypto for HipCrypto {
