@@ -364,6 +364,53 @@ class ConsensusCrypto:
         raise_for(code)
         return agg, bitmap, codes, taken
 
+    QC_GROUPS_MAX = 64   # include/ovhip.h OVH_QC_GROUPS_MAX
+
+    def build_qcs_raw(self, signatures, hashes, voters):
+        """ovh_build_qcs' raw arrays: (n_groups, group_hashes uint8[G, 32], out_sigs uint8[G, 96],
+        bitmaps uint8[G, bitmap_len], n_signed uint32[G], codes int32[n], taken bool[n],
+        group uint32[n]). out_sigs[g] is meaningful only where n_signed[g] > 0."""
+        n, sig, hs, pk = self._fixed(signatures, hashes, voters)
+        mg = self.QC_GROUPS_MAX
+        bl = (len(self.pubkeys) + 7) // 8
+        codes = np.zeros(max(n, 1), dtype=np.int32)
+        taken = np.zeros(max(n, 1), dtype=np.uint8)
+        group = np.zeros(max(n, 1), dtype=np.uint32)
+        gh = np.zeros((mg, 32), dtype=np.uint8)
+        out = np.zeros((mg, 96), dtype=np.uint8)
+        bm = np.zeros((mg, max(bl, 1)), dtype=np.uint8)
+        cnt = np.zeros(mg, dtype=np.uint32)
+        ng = ctypes.c_uint32(0)
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+        raise_for(self.lib.ovh_build_qcs(self.ctx.ptr, n, sig, hs, pk, ptr(codes), ptr(taken), ptr(group), mg,
+                                         ctypes.byref(ng), ptr(gh), ptr(out), ptr(bm), bl, ptr(cnt)))
+        g = int(ng.value)
+        return g, gh[:g], out[:g], bm[:g, :bl], cnt[:g], codes[:n], taken[:n].astype(bool), group[:n]
+
+    def build_qcs(self, signatures, hashes, voters):
+        """The QCs of a mixed-hash vote set in one device pass (ovh_build_qcs): every vote is
+        verified under its own hash, and each distinct hash (a group, numbered by first
+        appearance) gets its own selection and aggregate. Returns (qcs, codes, taken, group):
+        qcs[g] = (hash, aggregated_signature or None when no vote of the group is taken, bitmap,
+        n_signed); codes[i] the verify_signature result of vote i (also in the verdict cache),
+        taken bool[n], group[i] the index of vote i's QC. A validator with valid votes on two
+        hashes is taken in both groups: each QC stands alone."""
+        g, gh, out, bm, cnt, codes, taken, group = self.build_qcs_raw(signatures, hashes, voters)
+        qcs = [(gh[k].tobytes(), out[k].tobytes() if cnt[k] else None, bm[k].tobytes(), int(cnt[k])) for k in range(g)]
+        return qcs, codes, taken, group
+
+    def build_vote_qcs(self, signatures, votes, voters):
+        """The leader's inbox as ingress.decode_signed_vote delivers it: votes are (height, round,
+        vote_type, block_hash) tuples (an empty block_hash is the nil vote). The signed hashes come
+        from the device (vote_digests), then build_qcs. Returns (qcs, codes, taken, group) with
+        qcs[g] = (vote tuple, hash, aggregated_signature or None, bitmap, n_signed)."""
+        hashes = self.vote_digests(votes)
+        qcs, codes, taken, group = self.build_qcs(signatures, hashes, voters)
+        first = {}
+        for i, g in enumerate(group.tolist()):
+            first.setdefault(g, i)
+        return [(tuple(votes[first[g]]),) + q for g, q in enumerate(qcs)], codes, taken, group
+
     def build_proof(self, height: int, round_: int, block_hash: bytes, signatures, voters) -> bytes:
         """The overlord Proof of a block from the round's precommits: the vote hash
         hash(rlp(Vote{height, round, Precommit, block_hash})), build_qc over it, and the Proof's

@@ -47,6 +47,7 @@
 #include "fpvm.hpp"
 #include "keygen.hpp"
 #include "proof.hpp"
+#include "qc_segments.hpp"
 #include "rlp.hpp"
 #include "sm3.hpp"
 #include "sm3_bulk.hpp"
@@ -1795,18 +1796,21 @@ __global__ __launch_bounds__(64) void k_vm_g2tree(uint32_t m, VmDev prog, uint32
 }
 
 // projective (X : Y : Z) -> Jacobian (X Z, Y Z^2, Z) -> 96-byte compressed (one lane)
-__global__ __launch_bounds__(64) void k_g2p_compress(Slab in, uint8_t* out) {
-  if (threadIdx.x) return;
+__device__ __forceinline__ void g2p_compress(const Slab& in, uint32_t idx, uint8_t* out) {
   Fp2 X, Y, Z, zz;
-  in.ld2(X, 0, 0);
-  in.ld2(Y, 2, 0);
-  in.ld2(Z, 4, 0);
+  in.ld2(X, 0, idx);
+  in.ld2(Y, 2, idx);
+  in.ld2(Z, 4, idx);
   G2J j;
   fp2_mul(j.X, X, Z);
   fp2_sqr(zz, Z);
   fp2_mul(j.Y, Y, zz);
   j.Z = Z;
   g2_compress(out, j);
+}
+__global__ __launch_bounds__(64) void k_g2p_compress(Slab in, uint8_t* out) {
+  if (threadIdx.x) return;
+  g2p_compress(in, 0, out);
 }
 
 // Public keys from secret scalars (ovh_sk_to_pk, ovh_sk_to_pk_batch_device): program pkgen four
@@ -2430,6 +2434,10 @@ struct ValidatorTable {
   uint32_t* flags = nullptr;    // device PKF_* per entry
   // ovh_build_qc: owner (cap) | entry -> sorted rank (cap) | bitmap words (cap / 32) | count
   uint32_t* qc = nullptr;
+  // ovh_build_qcs, grown on demand (ensure_qcg): owner (groups x n) | bitmap words (groups x
+  // ceil(n / 32)) | counts (groups); the rank array stays in qc
+  uint32_t* qcg = nullptr;
+  size_t qcg_words = 0;
   std::vector<uint32_t> hflags;  // host copy
   std::vector<std::string> keys;
   std::unordered_map<std::string, uint32_t> index;  // key bytes -> first entry
@@ -4456,7 +4464,7 @@ static void destroy_one(ovh_ctx* c) {
   for (void* p : {(void*)c->in_buf, (void*)c->part_out, (void*)c->result, (void*)c->pool_q, (void*)c->pool_desc,
                   (void*)c->pool_scr, (void*)c->plog, (void*)c->vm_consts,
                   (void*)c->fin, (void*)c->scr, (void*)c->scr_pk, (void*)c->scr_sig, (void*)c->comb,
-                  (void*)c->tab.planes, (void*)c->tab.flags, (void*)c->tab.qc, (void*)c->qc_buf, (void*)c->qt_buf, (void*)c->hc_planes, (void*)c->hc_inf, (void*)c->gather,
+                  (void*)c->tab.planes, (void*)c->tab.flags, (void*)c->tab.qc, (void*)c->tab.qcg, (void*)c->qc_buf, (void*)c->qt_buf, (void*)c->hc_planes, (void*)c->hc_inf, (void*)c->gather,
                   (void*)c->mfin, (void*)c->sm1_plan, (void*)c->sm1_hash})
     if (p) (void)hipFree(p);
   for (void* p : c->vm_bufs) (void)hipFree(p);
@@ -5718,6 +5726,30 @@ int ovh_sm3_batch(ovh_ctx* c, size_t n, const uint8_t* data, const uint64_t* off
   return 0;
 }
 
+// ovh_build_qcs' outputs (build_qc_locked: null for ovh_build_qc)
+struct QcGroupsOut {
+  size_t max_groups;
+  uint32_t* group;  // may be null
+  uint32_t* n_groups;
+  uint8_t* group_hashes;
+  uint8_t* out_sigs;
+  uint8_t* bitmaps;
+  uint32_t* n_signed;
+};
+
+// The table's per-group selection scratch (ValidatorTable::qcg). No QC pass is in flight: they
+// are synchronous under c->mu.
+static int ensure_qcg(ovh_ctx* c, size_t words) {
+  ValidatorTable& t = c->tab;
+  if (t.qcg && t.qcg_words >= words) return 0;
+  if (t.qcg) (void)hipFree(t.qcg);
+  t.qcg = nullptr;
+  t.qcg_words = 0;
+  HIPCHK(hipMalloc(&t.qcg, words * 4));
+  t.qcg_words = words;
+  return 0;
+}
+
 // ovh_build_qc on one device (caller holds c->mu, the table is set): the round's verify batch on
 // the same-message path (every vote signs `hash`; its vote program leaves each sigma, affine and
 // subgroup-checked, in the slot's state slab), then on the batch's final stream, behind the
@@ -5725,9 +5757,16 @@ int ovh_sm3_batch(ovh_ctx* c, size_t n, const uint8_t* data, const uint64_t* off
 // One vote: the per-call check (verify_one_locked keeps no sigma), then sigma from one sigchk
 // launch without the subgroup check. One host synchronisation, after everything is enqueued; the
 // host staging lives until then.
+//
+// ovh_build_qcs (mo set, n >= 2): the same pass over the groups of a
+// mixed-hash batch. The plan's groups (distinct hashes, first seen in staged order) index the
+// selection's owner / bitmap / count arrays; the sum runs over the host's segment list
+// (qc_segments.hpp), one k_qc_upper workgroup and one compression per group; the host renumbers
+// the groups by first appearance in the caller's order when it writes the outputs. The single
+// outputs (out_sig, bitmap, n_signed) are unused then.
 static int build_qc_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* hashes, const uint8_t* pks,
                            int32_t* codes, uint8_t* taken, uint8_t* out_sig, uint8_t* bitmap, size_t bitmap_len,
-                           uint32_t* n_signed) {
+                           uint32_t* n_signed, const QcGroupsOut* mo = nullptr) {
   HIPCHK(hipSetDevice(c->device));
   const ValidatorTable& tb = c->tab;
   const uint32_t N = (uint32_t)n;
@@ -5736,13 +5775,25 @@ static int build_qc_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint
   const size_t t = table_split(c, n, pks, perm, tidx);
   SameMsgPlan pl;
   if (n >= 2) samemsg_plan(n, hashes, perm, pl);
-  // staging: sigs | (hashes) | pks | codes | table indices, the plan, then orig | taken | a zero
-  // offset and a code word (sigchk) | the 96 output bytes
+  const uint32_t G = mo ? pl.G : 1, bw = (tb.n + 31) / 32;
+  QcSegments sg;
+  if (mo) {  // the group count is decided here, before any device work
+    if (G > OVH_QC_GROUPS_MAX || G > mo->max_groups) return OVH_ERR_ARG;
+    qc_segments(n, G, pl.gid.data(), sg);
+  }
+  const size_t lbytes = 4 * (sg.list.size() + sg.seg.size());
+  // staging: sigs | (hashes) | pks | codes | table indices, the plan (and the segment list and
+  // table), then orig | taken | a zero offset and a code word (sigchk) | 96 output bytes per group
   pl.off = (n * (96 + 32 + 48 + 4 + 4) + 255) / 256 * 256;
-  const size_t qoff = (pl.off + pl.bytes + 255) / 256 * 256;
+  const size_t qoff = (pl.off + pl.bytes + lbytes + 255) / 256 * 256;
   const size_t zoff = qoff + 8 * n, ooff = zoff + 16;
-  CHK(ensure_in(c, ooff + 96));
-  CHK(ensure_cap(c, n));
+  CHK(ensure_in(c, ooff + 96 * (size_t)G));
+  // the padded segments' tree (32 entries per chunk, <= n / 2 + 32 G) has to fit the slot's MSM
+  // tree slab, msm_acap(cap) entries: 64 singleton groups need 2,048 against 2,044 at cap 256
+  const size_t ecap = sg.entries > MSM_NB ? (sg.entries - MSM_NB + 3) / 4 : 0;
+  CHK(ensure_cap(c, ecap > n ? ecap : n));
+  if (msm_acap(c->cap) < sg.entries) return OVH_ERR_ARG;
+  if (mo) CHK(ensure_qcg(c, (size_t)G * ((size_t)tb.n + bw + 1)));
   uint8_t* d = c->in_buf;
   int32_t* dc = (int32_t*)(d + n * 176);
   const int32_t* dtidx = (const int32_t*)(d + n * 180);
@@ -5750,9 +5801,8 @@ static int build_qc_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint
   uint32_t* dtaken = dorig + n;
   std::vector<uint8_t> hb, hp;
   std::vector<int32_t> pc(n);
-  std::vector<uint32_t> ptk(n);
-  uint32_t cnt = 0;
-  uint8_t sig96[96];
+  std::vector<uint32_t> ptk(n), cnts(G, 0), hbm(mo ? (size_t)G * bw : 0);
+  std::vector<uint8_t> sig96(96 * (size_t)G);
   // an error return drains the streams that copy from / into the host buffers above before they
   // die; the normal return has waited already (the call's one synchronisation)
   struct Drain {
@@ -5787,12 +5837,16 @@ static int build_qc_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint
     slot = c->last_slot;
     st = c->stream;
   } else {
-    hp.resize(pl.bytes);
+    hp.resize(pl.bytes + lbytes);
     memcpy(hp.data(), pl.gid.data(), 4 * n);
     memcpy(hp.data() + 4 * n, pl.ghash.data(), 32 * (size_t)pl.G);
     memcpy(hp.data() + 4 * n + 32 * (size_t)pl.G, pl.head.data(), 4 * (size_t)pl.G);
     if (!pl.pairs.empty()) memcpy(hp.data() + 4 * n + 36 * (size_t)pl.G, pl.pairs.data(), 4 * pl.pairs.size());
-    HIPCHK(hipMemcpyAsync(d + pl.off, hp.data(), pl.bytes, hipMemcpyHostToDevice, c->stream));
+    if (mo) {
+      memcpy(hp.data() + pl.bytes, sg.list.data(), 4 * sg.list.size());
+      memcpy(hp.data() + pl.bytes + 4 * sg.list.size(), sg.seg.data(), 4 * sg.seg.size());
+    }
+    HIPCHK(hipMemcpyAsync(d + pl.off, hp.data(), hp.size(), hipMemcpyHostToDevice, c->stream));
     const uint8_t* ex = d + pl.off;
     const uint32_t* head = (const uint32_t*)(ex + 4 * n + 32 * (size_t)pl.G);
     const SameMsgDev pd{pl.G, (const uint32_t*)ex, ex + 4 * n, head, head + pl.G, &pl.level_off};
@@ -5806,31 +5860,52 @@ static int build_qc_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint
   sel.codes = dc;
   sel.tidx = dtidx;
   sel.orig = perm.empty() ? nullptr : dorig;
-  sel.owner = tb.qc;
   sel.rank = tb.qc + tb.cap;
-  sel.bitmap = tb.qc + 2 * (size_t)tb.cap;
-  sel.count = sel.bitmap + tb.cap / 32;
-  sel.taken = dtaken;
-  k_qc_reset<<<nblk(tb.n), WG, 0, st>>>(tb.n, sel);
-  if (t) k_qc_claim<<<nblk(t), WG, 0, st>>>((uint32_t)t, sel);
-  k_qc_mark<<<nblk(n), WG, 0, st>>>(N, (uint32_t)t, sel);
-  if (n == 1) {
-    constexpr uint32_t SL = 64 / VM_SIGCHK_W;
-    k_vm_sigchk<<<(1 + SL - 1) / SL, 64, LDS_SIGCHK, st>>>(1, c->vm_sigchk, c->vm_consts, d, (const uint64_t*)(d + zoff), 0,
-                                                           (int32_t*)(d + zoff + 8), a.A);
+  sel.gid = nullptr;
+  sel.groups = G;
+  sel.bw = bw;
+  if (mo) {
+    sel.gid = (const uint32_t*)(d + pl.off);
+    sel.owner = tb.qcg;
+    sel.bitmap = sel.owner + (size_t)G * tb.n;
+    sel.count = sel.bitmap + (size_t)G * bw;
   } else {
-    k_qc_chunk<<<(N + MSM_CH - 1) >> MSM_CH_LV, 64, LDS_MSM8, st>>>(N, dtaken, c->vm_madd, c->vm_padd, MSM8_STRIDE_W,
-                                                                   c->vm_consts, a);
-    if (N > MSM_CH) k_qc_upper<<<1, 64, LDS_MSM8, st>>>(N, c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
+    sel.owner = tb.qc;
+    sel.bitmap = tb.qc + 2 * (size_t)tb.cap;
+    sel.count = sel.bitmap + tb.cap / 32;
   }
-  k_g2p_compress<<<1, 64, 0, st>>>(a.A, d + ooff);
+  sel.taken = dtaken;
+  k_qc_reset<<<nblk((size_t)G * tb.n), WG, 0, st>>>(tb.n, sel);
+  if (t) k_qc_claim<<<nblk(t), WG, 0, st>>>(tb.n, (uint32_t)t, sel);
+  k_qc_mark<<<nblk(n), WG, 0, st>>>(tb.n, N, (uint32_t)t, sel);
+  if (mo) {
+    const uint32_t* dlist = (const uint32_t*)(d + pl.off + pl.bytes);
+    const uint32_t* dseg = dlist + sg.list.size();
+    k_qc_chunk<true><<<sg.chunks, 64, LDS_MSM8, st>>>(N, dtaken, dlist, c->vm_madd, c->vm_padd, MSM8_STRIDE_W,
+                                                     c->vm_consts, a);
+    if (sg.chunks > G)  // a group of more than one chunk
+      k_qc_upper<true><<<G, 64, LDS_MSM8, st>>>(0, dseg, c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
+    k_qc_compress<<<G, 64, 0, st>>>(a.A, dseg, d + ooff);
+  } else {
+    if (n == 1) {
+      constexpr uint32_t SL = 64 / VM_SIGCHK_W;
+      k_vm_sigchk<<<(1 + SL - 1) / SL, 64, LDS_SIGCHK, st>>>(1, c->vm_sigchk, c->vm_consts, d, (const uint64_t*)(d + zoff),
+                                                             0, (int32_t*)(d + zoff + 8), a.A);
+    } else {
+      k_qc_chunk<false><<<(N + MSM_CH - 1) >> MSM_CH_LV, 64, LDS_MSM8, st>>>(N, dtaken, nullptr, c->vm_madd, c->vm_padd,
+                                                                            MSM8_STRIDE_W, c->vm_consts, a);
+      if (N > MSM_CH) k_qc_upper<false><<<1, 64, LDS_MSM8, st>>>(N, nullptr, c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
+    }
+    k_g2p_compress<<<1, 64, 0, st>>>(a.A, d + ooff);
+  }
   HIPCHK(hipGetLastError());
   drain.s[1] = st;
   HIPCHK(hipMemcpyAsync(pc.data(), dc, 4 * n, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(ptk.data(), dtaken, 4 * n, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(bitmap, sel.bitmap, bitmap_len, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(&cnt, sel.count, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(sig96, d + ooff, 96, hipMemcpyDeviceToHost, st));
+  if (mo) HIPCHK(hipMemcpyAsync(hbm.data(), sel.bitmap, 4 * hbm.size(), hipMemcpyDeviceToHost, st));
+  else HIPCHK(hipMemcpyAsync(bitmap, sel.bitmap, bitmap_len, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(cnts.data(), sel.count, 4 * (size_t)G, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(sig96.data(), d + ooff, sig96.size(), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   drain.armed = false;
   CHK(pool_failed(c));
@@ -5839,9 +5914,30 @@ static int build_qc_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint
     codes[i] = pc[j];
     if (taken) taken[i] = (uint8_t)ptk[j];
   }
-  *n_signed = cnt;
-  if (!cnt) return BLST_AGGR_TYPE_MISMATCH;
-  memcpy(out_sig, sig96, 96);
+  if (mo) {
+    // the plan numbers the groups in staged order (table votes first): renumber by first
+    // appearance in the caller's order
+    std::vector<uint32_t> og(n), cmap(G, QC_NONE);
+    for (size_t j = 0; j < n; ++j) og[perm.empty() ? j : perm[j]] = pl.gid[j];
+    uint32_t next = 0;
+    for (size_t i = 0; i < n; ++i) {
+      uint32_t& m = cmap[og[i]];
+      if (m == QC_NONE) m = next++;
+      if (mo->group) mo->group[i] = m;
+    }
+    for (uint32_t g = 0; g < G; ++g) {
+      const size_t o = cmap[g];
+      memcpy(mo->group_hashes + 32 * o, &pl.ghash[32 * (size_t)g], 32);
+      memcpy(mo->bitmaps + bitmap_len * o, &hbm[(size_t)g * bw], bitmap_len);
+      mo->n_signed[o] = cnts[g];
+      if (cnts[g]) memcpy(mo->out_sigs + 96 * o, &sig96[96 * (size_t)g], 96);
+    }
+    *mo->n_groups = G;
+    return 0;
+  }
+  *n_signed = cnts[0];
+  if (!cnts[0]) return BLST_AGGR_TYPE_MISMATCH;
+  memcpy(out_sig, sig96.data(), 96);
   return 0;
 }
 
@@ -5861,6 +5957,34 @@ int ovh_build_qc(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* hash,
     r = build_qc_locked(s, n, sigs, hashes.data(), pks, codes, taken, out_sig, bitmap, bitmap_len, n_signed);
   }
   if (r == 0 || r == BLST_AGGR_TYPE_MISMATCH) cache_put(c, n, sigs, hashes.data(), pks, codes);
+  return r;
+}
+
+int ovh_build_qcs(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* hashes, const uint8_t* pks, int32_t* codes,
+                  uint8_t* taken, uint32_t* group, size_t max_groups, uint32_t* n_groups, uint8_t* group_hashes,
+                  uint8_t* out_sigs, uint8_t* bitmaps, size_t bitmap_len, uint32_t* n_signed) {
+  if (!c || !sigs || !hashes || !pks || !codes || !n_groups || !group_hashes || !out_sigs || !bitmaps || !n_signed)
+    return OVH_ERR_ARG;
+  if (n == 0 || n > (1u << 24) || max_groups == 0) return OVH_ERR_ARG;
+  int r;
+  {
+    ovh_ctx* s = c->sub.empty() ? c : c->sub[0];
+    std::lock_guard<std::mutex> g(s->mu);
+    if (!s->tab.n || bitmap_len != ((size_t)s->tab.n + 7) / 8) return OVH_ERR_ARG;
+    if (n == 1) {  // the per-call path of ovh_build_qc; an empty QC is no error here
+      r = build_qc_locked(s, 1, sigs, hashes, pks, codes, taken, out_sigs, bitmaps, bitmap_len, n_signed);
+      if (r == BLST_AGGR_TYPE_MISMATCH) r = 0;
+      if (r == 0) {
+        memcpy(group_hashes, hashes, 32);
+        if (group) group[0] = 0;
+        *n_groups = 1;
+      }
+    } else {
+      const QcGroupsOut mo{max_groups, group, n_groups, group_hashes, out_sigs, bitmaps, n_signed};
+      r = build_qc_locked(s, n, sigs, hashes, pks, codes, taken, nullptr, nullptr, bitmap_len, nullptr, &mo);
+    }
+  }
+  if (r == 0) cache_put(c, n, sigs, hashes, pks, codes);
   return r;
 }
 

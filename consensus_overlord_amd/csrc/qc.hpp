@@ -9,6 +9,7 @@
 //                of one 64-vote chunk per one-wave workgroup
 //   k_qc_upper   the levels above, one workgroup over the chunk sums (loops over the pairs of a
 //                level, so the launch count does not grow with log2 n)
+//   k_qc_compress the groups' sums to 96 bytes each (ovh_build_qcs)
 // The sum reads the sigma planes the same-message vote program left in the state slab (affine,
 // decompressed and subgroup-checked once); a vote that is not taken contributes the identity.
 // The kernels keep the MSM kernels' rules: no workgroup waits for another, the levels of a
@@ -19,12 +20,19 @@
 
 #define QC_NONE 0xFFFFFFFFu
 
+// ovh_build_qcs runs the same kernels over the groups of a mixed-hash
+// batch (one group per distinct hash): the selection indexes owner, bitmap and count by the
+// vote's group, and the sum reads its votes through the host's segment list (qc_segments.hpp:
+// a group's votes contiguous and padded to whole chunks), one k_qc_upper workgroup per group.
 struct QcSel {
   const int32_t* codes;  // final per-vote codes, staged order
   const int32_t* tidx;   // table entry of staged vote j < t (first entry of a duplicate key)
   const uint32_t* orig;  // the caller's index of staged vote j (null: j)
   const uint32_t* rank;  // table entry -> its position in key-sorted order (the bitmap's bit)
-  uint32_t* owner;       // per table entry: the lowest caller's index of a valid vote
+  const uint32_t* gid;   // group of staged vote j (null: one group)
+  uint32_t groups;       // owner[g * tn + e], bitmap[g * bw + word], count[g]
+  uint32_t bw;           // bitmap words of a group: ceil(tn / 32)
+  uint32_t* owner;       // per group and table entry: the lowest caller's index of a valid vote
   uint32_t* bitmap;      // MSB-first bytes, written as words
   uint32_t* count;
   uint32_t* taken;       // per staged vote: 1 or 0
@@ -32,30 +40,39 @@ struct QcSel {
 
 __global__ __launch_bounds__(WG) void k_qc_reset(uint32_t tn, QcSel s) {
   const uint32_t e = blockIdx.x * WG + threadIdx.x;
-  if (e < tn) s.owner[e] = QC_NONE;
-  if (e < (tn + 31) / 32) s.bitmap[e] = 0;
-  if (e == 0) *s.count = 0;
+  if (e < s.groups * tn) s.owner[e] = QC_NONE;
+  if (e < s.groups * s.bw) s.bitmap[e] = 0;
+  if (e < s.groups) s.count[e] = 0;
 }
 
-__global__ __launch_bounds__(WG) void k_qc_claim(uint32_t t, QcSel s) {
+__global__ __launch_bounds__(WG) void k_qc_claim(uint32_t tn, uint32_t t, QcSel s) {
   const uint32_t j = blockIdx.x * WG + threadIdx.x;
-  if (j < t && s.codes[j] == 0) atomicMin(&s.owner[s.tidx[j]], s.orig ? s.orig[j] : j);
+  if (j < t && s.codes[j] == 0) {
+    const uint32_t g = s.gid ? s.gid[j] : 0u;
+    atomicMin(&s.owner[g * tn + (uint32_t)s.tidx[j]], s.orig ? s.orig[j] : j);
+  }
 }
 
-__global__ __launch_bounds__(WG) void k_qc_mark(uint32_t n, uint32_t t, QcSel s) {
+__global__ __launch_bounds__(WG) void k_qc_mark(uint32_t tn, uint32_t n, uint32_t t, QcSel s) {
   const uint32_t j = blockIdx.x * WG + threadIdx.x;
   bool tk = false;
+  uint32_t g = 0;
   if (j < t && s.codes[j] == 0) {
     const uint32_t e = (uint32_t)s.tidx[j];
-    tk = s.owner[e] == (s.orig ? s.orig[j] : j);
+    if (s.gid) g = s.gid[j];
+    tk = s.owner[g * tn + e] == (s.orig ? s.orig[j] : j);
     if (tk) {
       const uint32_t k = s.rank[e];  // bit k: byte k / 8, MSB first (little-endian words)
-      atomicOr(&s.bitmap[k >> 5], 1u << (8 * ((k >> 3) & 3) + 7 - (k & 7)));
+      atomicOr(&s.bitmap[g * s.bw + (k >> 5)], 1u << (8 * ((k >> 3) & 3) + 7 - (k & 7)));
     }
   }
   if (j < n) s.taken[j] = tk ? 1u : 0u;
-  const uint32_t c = (uint32_t)__popcll(__ballot(tk));
-  if (threadIdx.x == 0 && c) atomicAdd(s.count, c);
+  if (s.gid) {  // uniform
+    if (tk) atomicAdd(&s.count[g], 1u);
+  } else {
+    const uint32_t c = (uint32_t)__popcll(__ballot(tk));
+    if (threadIdx.x == 0 && c) atomicAdd(s.count, c);
+  }
 }
 
 // Levels 0 .. MSM_CH_LV - 1 of the masked sum: workgroup g owns votes 64 g .. 64 g + 63 and the
@@ -63,12 +80,18 @@ __global__ __launch_bounds__(WG) void k_qc_mark(uint32_t n, uint32_t t, QcSel s)
 // k .. k + 2^(l+1) - 1 after level l. Level 0 is madd over the taken votes of a pair (the one
 // taken vote and the identity, or -- none taken -- the identity written directly: madd's first
 // operand is affine); the chunk's sum ends in A[32 g].
-__global__ __launch_bounds__(64) void k_qc_chunk(uint32_t n, const uint32_t* __restrict__ taken, VmDev madd, VmDev padd,
+// SEG: the chunk's votes are list[64 g ..] (staged indices, then QC_NONE pads to the chunk's end;
+// at least one vote), so a chunk never holds votes of two groups.
+template <bool SEG>
+__global__ __launch_bounds__(64) void k_qc_chunk(uint32_t n, const uint32_t* __restrict__ taken,
+                                                 const uint32_t* __restrict__ list, VmDev madd, VmDev padd,
                                                  uint32_t stride_w, const uint32_t* __restrict__ cst_g, MsmArgs a) {
   constexpr uint32_t W = VM_MADD_W, SL = 64 / W;
-  MSM_VM_PROLOGUE(W);
   const uint32_t k0 = blockIdx.x << MSM_CH_LV, a0 = k0 >> 1;
-  const uint32_t m = n - k0 < MSM_CH ? n - k0 : MSM_CH;  // the chunk's votes (>= 1)
+  uint32_t m;  // the chunk's votes (>= 1)
+  if (SEG) m = (uint32_t)__popcll(__ballot(list[k0 + threadIdx.x] != QC_NONE));
+  else m = n - k0 < MSM_CH ? n - k0 : MSM_CH;
+  MSM_VM_PROLOGUE(W);
   for (uint32_t lv = 0; lv < MSM_CH_LV && (lv == 0 || (1u << lv) < m); ++lv) {
     const uint32_t h = 1u << lv;
     const uint32_t np = lv == 0 ? (m + 1) / 2 : (m - h + 2 * h - 1) >> (lv + 1);
@@ -81,8 +104,9 @@ __global__ __launch_bounds__(64) void k_qc_chunk(uint32_t n, const uint32_t* __r
       if (lv == 0) {
         ka = SRC_PT, kb = SRC_ID, ia = ib = 0;
         if (act) {
-          const uint32_t i0 = k0 + k, i1 = i0 + 1;
-          const bool t0 = taken[i0] != 0, t1 = i1 < n && taken[i1] != 0;
+          const bool two = k + 1 < m;
+          const uint32_t i0 = SEG ? list[k0 + k] : k0 + k, i1 = !two ? 0u : SEG ? list[k0 + k + 1] : i0 + 1;
+          const bool t0 = taken[i0] != 0, t1 = two && taken[i1] != 0;
           if (t0) {
             ia = 2 * i0;
             if (t1) kb = SRC_PT, ib = 2 * i1;
@@ -107,16 +131,32 @@ __global__ __launch_bounds__(64) void k_qc_chunk(uint32_t n, const uint32_t* __r
 
 // Levels >= MSM_CH_LV: one workgroup adds the chunk sums (the entries of votes 64 j, A[32 j])
 // level by level into A[0], eight pairs per run of the wave.
-__global__ __launch_bounds__(64) void k_qc_upper(uint32_t n, VmDev padd, uint32_t stride_w,
-                                                 const uint32_t* __restrict__ cst_g, MsmArgs a) {
+// SEG: workgroup g adds the chunk sums of group g (chunks seg[2 g] .. + seg[2 g + 1] - 1, whole
+// chunks: the levels above a chunk see 64 votes in each) into the first entry of its segment.
+template <bool SEG>
+__global__ __launch_bounds__(64) void k_qc_upper(uint32_t n, const uint32_t* __restrict__ seg, VmDev padd,
+                                                 uint32_t stride_w, const uint32_t* __restrict__ cst_g, MsmArgs a) {
   constexpr uint32_t W = VM_PADD_W, SL = 64 / W;
+  uint32_t a0 = 0;
+  if (SEG) {
+    n = seg[2 * blockIdx.x + 1] << MSM_CH_LV;
+    if (n <= MSM_CH) return;  // one chunk: its sum is the group's
+    a0 = seg[2 * blockIdx.x] << (MSM_CH_LV - 1);
+  }
   MSM_VM_PROLOGUE(W);
   for (uint32_t lv = MSM_CH_LV; lv < 32 && (1u << lv) < n; ++lv) {
     const uint32_t h = 1u << lv, np = (n - h + 2 * h - 1) >> (lv + 1);
     for (uint32_t r = 0; r < np; r += SL) {
       const uint32_t p = r + slice, k = p << (lv + 1);
-      const uint32_t ia = k >> 1, ib = (k + h) >> 1;
+      const uint32_t ia = a0 + (k >> 1), ib = a0 + ((k + h) >> 1);
       msm_pair_op<W>(padd, VM_PADD_NIN, slots, cst, lane, p < np, a, SRC_A, ia, SRC_A, ib, SRC_A, ia);
     }
   }
+}
+
+// The groups' sums, projective (X : Y : Z) in the first entry of each segment -> 96-byte
+// compressed (g2p_compress: one lane per group's workgroup, as k_g2p_compress)
+__global__ __launch_bounds__(64) void k_qc_compress(Slab in, const uint32_t* __restrict__ seg, uint8_t* out) {
+  if (threadIdx.x) return;
+  g2p_compress(in, seg[2 * blockIdx.x] << (MSM_CH_LV - 1), out + 96 * (size_t)blockIdx.x);
 }

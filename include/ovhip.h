@@ -258,6 +258,44 @@ int ovh_build_qc(ovh_ctx* ctx, size_t n, const uint8_t* sigs /* n x 96 */, const
                  const uint8_t* pks /* n x 48 */, int32_t* codes /* n */, uint8_t* taken /* n, may be NULL */,
                  uint8_t out_sig[96], uint8_t* bitmap, size_t bitmap_len, uint32_t* n_signed);
 
+/* The QCs of a mixed-hash vote set in one device pass: a leader's inbox as it arrives (the votes
+ * of one (height, round, type) split between the block hash and the nil vote, late votes of the
+ * previous round beside them), without knowing the winning hash first and without one device pass
+ * per hash. One verify batch over all n votes (one hash_to_G2 and one Miller loop per distinct
+ * hash, one MSM, one final exponentiation, exact per-vote bisection), then per distinct hash the
+ * selection, the sum of the taken signatures and its compression, behind one synchronisation.
+ * sigs n x 96 B, hashes n x 32 B, pks n x 48 B; needs ovh_set_validators. Host buffers,
+ * synchronous, thread-safe; a multi-device context runs it on its first device. One vote (n == 1)
+ * takes the per-call path, as in ovh_build_qc.
+ *   groups        the distinct values among the rows of `hashes`, numbered by first appearance in
+ *                 the caller's order. group[i] (may be NULL) is vote i's group, group_hashes[g]
+ *                 that group's 32-byte hash, *n_groups their number G.
+ *   codes[i]      exactly the ovh_verify(sig_i, hashes_i, pk_i) result of every vote, each under
+ *                 its own hash. The verdicts enter the verdict cache as ovh_prefetch's do.
+ *   taken[i]      (may be NULL) vote i is taken iff codes[i] == 0, its voter is in the validator
+ *                 table, and no vote with a lower index of the same voter in the same group is
+ *                 taken. A voter with valid votes in two groups (equivocation) is taken in both:
+ *                 each QC stands alone, and what to do about the equivocation is the caller's
+ *                 business.
+ *   out_sigs[g]   (96 B each) the compressed sum of group g's taken signatures; not written for a
+ *                 group with n_signed[g] == 0.
+ *   bitmaps[g]    (bitmap_len == ceil(table size / 8) bytes each) ovh_build_qc's bitmap rule per
+ *                 group: MSB first over the key-sorted table, a duplicated table key counts at its
+ *                 first sorted position, pad bits 0; all zero for a group without a taken vote.
+ *   n_signed[g]   the number of taken votes of group g.
+ * Returns 0 whenever the outputs were written, also when some or all groups are empty (the caller
+ * reads n_signed); OVH_ERR_ARG for a NULL required pointer, no validator table, a wrong
+ * bitmap_len, n == 0, n > 2^24, max_groups == 0, or more distinct hashes than
+ * min(max_groups, OVH_QC_GROUPS_MAX) -- the group count is decided on the host before any device
+ * work, and nothing is written; device / RNG errors as elsewhere. With every row of `hashes`
+ * equal, codes, taken, bitmap, count and the 96 signature bytes equal ovh_build_qc's. */
+#define OVH_QC_GROUPS_MAX 64
+int ovh_build_qcs(ovh_ctx* ctx, size_t n, const uint8_t* sigs /* n x 96 */, const uint8_t* hashes /* n x 32 */,
+                  const uint8_t* pks /* n x 48 */, int32_t* codes /* n */, uint8_t* taken /* n, may be NULL */,
+                  uint32_t* group /* n, may be NULL */, size_t max_groups, uint32_t* n_groups,
+                  uint8_t* group_hashes /* max_groups x 32 */, uint8_t* out_sigs /* max_groups x 96 */,
+                  uint8_t* bitmaps /* max_groups x bitmap_len */, size_t bitmap_len, uint32_t* n_signed /* max_groups */);
+
 /* TESTS ONLY (context created with OVH_FLAG_TEST_RLC, else OVH_ERR_ARG): vote i of every
  * following batch gets the coefficient SplitMix64(seed, index_base + i). Predictable
  * coefficients let an adversary cancel invalid signatures inside the combined check

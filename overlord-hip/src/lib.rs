@@ -272,6 +272,43 @@ impl HipCrypto {
         Ok((Bytes::copy_from_slice(&out), Bytes::from(bitmap), codes, taken))
     }
 
+    /// The QCs of a mixed-hash vote set in one device pass (`ovh_build_qcs`): the leader's inbox as
+    /// it arrives, every vote verified under its own hash, one QC per distinct hash. Returns the
+    /// groups in order of first appearance as (hash, signature or `None` when no vote of the
+    /// group is taken, bitmap, number of taken votes), then the per-vote codes, taken flags and
+    /// group numbers. A validator with valid votes on two hashes is taken in both groups: each QC
+    /// stands alone, the equivocation is the caller's to handle. `CryptoErr(OVH_ERR_ARG)` for more
+    /// than `OVH_QC_GROUPS_MAX` distinct hashes. Blocking.
+    #[allow(clippy::type_complexity)]
+    pub fn build_qcs(&self, sigs: &[[u8; 96]], hashes: &[[u8; 32]], voters: &[[u8; 48]]) -> Result<(Vec<([u8; 32], Option<Bytes>, Bytes, u32)>, Vec<i32>, Vec<u8>, Vec<u32>), Box<dyn Error + Send>> {
+        if sigs.len() != hashes.len() || sigs.len() != voters.len() {
+            return Err(to_err(ffi::OVH_ERR_LEN_MISMATCH));
+        }
+        let bl = (self.pubkeys.blocking_read().len() + 7) / 8;
+        let mg = ffi::OVH_QC_GROUPS_MAX;
+        let mut codes = vec![0i32; sigs.len()];
+        let mut taken = vec![0u8; sigs.len()];
+        let mut group = vec![0u32; sigs.len()];
+        let mut n_groups = 0u32;
+        let mut group_hashes = vec![[0u8; 32]; mg];
+        let mut out_sigs = vec![[0u8; 96]; mg];
+        let mut bitmaps = vec![0u8; mg * bl];
+        let mut n_signed = vec![0u32; mg];
+        check(unsafe {
+            ffi::ovh_build_qcs(self.raw(), sigs.len(), sigs.as_ptr() as *const u8, hashes.as_ptr() as *const u8,
+                               voters.as_ptr() as *const u8, codes.as_mut_ptr(), taken.as_mut_ptr(), group.as_mut_ptr(),
+                               mg, &mut n_groups, group_hashes.as_mut_ptr() as *mut u8, out_sigs.as_mut_ptr() as *mut u8,
+                               bitmaps.as_mut_ptr(), bl, n_signed.as_mut_ptr())
+        })?;
+        let qcs = (0..n_groups as usize)
+            .map(|g| {
+                let sig = if n_signed[g] > 0 { Some(Bytes::copy_from_slice(&out_sigs[g])) } else { None };
+                (group_hashes[g], sig, Bytes::copy_from_slice(&bitmaps[g * bl..(g + 1) * bl]), n_signed[g])
+            })
+            .collect();
+        Ok((qcs, codes, taken, group))
+    }
+
     /// `Crypto::hash` of many messages on the device (`ovh_sm3_batch`: one lane per message),
     /// digest i = SM3(msgs[i]). Blocking.
     pub fn hash_batch(&self, msgs: &[Bytes]) -> Result<Vec<[u8; 32]>, Box<dyn Error + Send>> {
