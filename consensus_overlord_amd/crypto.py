@@ -87,12 +87,15 @@ def _concat(items: Sequence[bytes]):
 
 class Context:
     """One libovhip context (device memory, streams, DST) on HIP device `device`, or over
-    several devices of this process (`devices=[...]`, ovh_create_multi)."""
+    several devices of this process (`devices=[...]`, ovh_create_multi). `dst`: None for the
+    default DST, else 0-255 bytes (b"" is the empty DST); a longer one raises ValueError."""
 
     def __init__(self, device: int = 0, dst: Optional[bytes] = None, flags: int = 0,
                  devices: Optional[Sequence[int]] = None):
         self.lib = _lib.load()
         d = None if dst is None else bytes(dst)
+        if d is not None and len(d) > 255:
+            raise ValueError("the DST is 0-255 bytes (RFC 9380 5.3.1), got %d" % len(d))
         if devices:
             arr = (ctypes.c_int * len(devices))(*devices)
             self.ptr = self.lib.ovh_create_multi(arr, len(devices), d, 0 if d is None else len(d), flags)

@@ -76,7 +76,8 @@ OVH_HD void sha256_iv(uint32_t st[8]) {
 // bytes at words 0..7 of the first template block of each chain.
 //   b_0 = H(Z_pad || msg || I2OSP(256,2) || 0x00 || DST || len)   -> state after Z_pad = mid0
 //   b_i = H(strxor(b_0, b_{i-1}) || I2OSP(i,1) || DST || len)      -> counter byte at byte 32
-#define OVH_XMD_MAX_BLOCKS 4
+// OVH_XMD_MAX_BLOCKS = 5 holds every DST of 0..255 bytes (b_0 tail: 36 + L + 9 <= 300 bytes).
+#define OVH_XMD_MAX_BLOCKS 5
 struct XmdTemplates {
   uint32_t mid0[8];                        // SHA-256 state after the all-zero Z_pad block
   uint32_t b0[OVH_XMD_MAX_BLOCKS][16];     // blocks after Z_pad (words 0..7 of b0[0] <- msg)
@@ -84,9 +85,12 @@ struct XmdTemplates {
   uint32_t nb0, nbi;
 };
 
-// Host-side template construction (also callable in the host test build).
-inline bool xmd_build_templates(XmdTemplates& t, const uint8_t* dst, uint32_t dst_len) {
-  if (dst_len > 255) return false;
+// Host-side template construction (also callable in the host test build). The DST is 0..255
+// bytes (RFC 9380 5.3.1); a longer one is refused (the hashed oversize DST of 5.3.3 is not
+// implemented). The length arrives as size_t so that no caller truncates it before this check.
+inline bool xmd_build_templates(XmdTemplates& t, const uint8_t* dst, size_t dst_len_) {
+  if (dst_len_ > 255 || (!dst && dst_len_ != 0)) return false;
+  const uint32_t dst_len = (uint32_t)dst_len_;
   uint8_t buf[OVH_XMD_MAX_BLOCKS * 64];
   // b0 tail: msg(32) | 0x01 0x00 | 0x00 | DST | len, then padding; total message = 64 + 36 + L
   {
@@ -277,12 +281,10 @@ OVH_HDNI void iso_map_g2(G2J& r, const Fp2& x, const Fp2& y) {
   fp2_mul(r.Y, t, y);
 }
 
-// Full hash_to_curve for one 32-byte message (single lane).
-OVH_HDNI void hash_to_g2(G2J& r, const uint32_t msg[8], const XmdTemplates& t) {
-  uint32_t uni[64];
-  expand_message_xmd_256(uni, msg, t);
-  Fp2 u0, u1, x, y;
-  hash_to_field_fp2x2(u0, u1, uni);
+// The curve half of hash_to_curve: SSWU and the isogeny on u0 and u1, the sum, the cofactor
+// clearing (u0 = u1 is a doubling, u1 = -u0 gives the identity).
+OVH_HDNI void map2_to_g2(G2J& r, const Fp2& u0, const Fp2& u1) {
+  Fp2 x, y;
   G2J q0, q1;
   map_to_curve_sswu(x, y, u0);
   iso_map_g2(q0, x, y);
@@ -290,6 +292,15 @@ OVH_HDNI void hash_to_g2(G2J& r, const uint32_t msg[8], const XmdTemplates& t) {
   iso_map_g2(q1, x, y);
   jac_add(q0, q0, q1);
   g2_clear_cofactor(r, q0);
+}
+
+// Full hash_to_curve for one 32-byte message (single lane).
+OVH_HDNI void hash_to_g2(G2J& r, const uint32_t msg[8], const XmdTemplates& t) {
+  uint32_t uni[64];
+  expand_message_xmd_256(uni, msg, t);
+  Fp2 u0, u1;
+  hash_to_field_fp2x2(u0, u1, uni);
+  map2_to_g2(r, u0, u1);
 }
 
 }  // namespace ovh

@@ -4343,7 +4343,8 @@ ovh_ctx* ovh_create(int device, const uint8_t* dst, size_t dst_len, uint32_t fla
   // default): the four final streams fill the low-priority set one queue each, the pool streams
   // draw from the high-priority set and ovh_stream from the normal one. A fifth stream of one
   // priority shares a queue and runs in order behind another.
-  bool ok = xmd_build_templates(c->xmd, dst, (uint32_t)dst_len) &&
+  // a DST of more than 255 bytes is refused here (xmd_build_templates takes the whole size_t)
+  bool ok = xmd_build_templates(c->xmd, dst, dst_len) &&
             stream_new(&c->stream, 0) == hipSuccess &&
             stream_new(&c->fstream, lo) == hipSuccess &&
             stream_new(&c->fstream2, lo) == hipSuccess &&

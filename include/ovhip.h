@@ -67,6 +67,8 @@ typedef struct ovh_ctx ovh_ctx;
 
 /* Create a context on HIP device `device` with hash-to-curve domain separation tag `dst`
  * (NULL -> "BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_NUL_", the believed ophelia-blst DST).
+ * `dst` is 0-255 bytes (RFC 9380 5.3.1); longer returns NULL (the hashed oversize DST of 5.3.3
+ * is not implemented); `dst != NULL` with length 0 is the empty DST.
  * Replaces ConsensusCrypto::new's crypto state (src/consensus.rs:347-359). NULL on failure. */
 ovh_ctx* ovh_create(int device, const uint8_t* dst, size_t dst_len, uint32_t flags);
 /* One context over several GPUs of this process: ovh_verify_batch and

@@ -1,6 +1,7 @@
 // Device probe for the unit-level arithmetic tests (tests/test_gpu_fp_bounds.py): the field
-// primitives of csrc/bls/fp.hpp and csrc/fpvm.hpp, one thread per case, and a runner for Fp-VM
-// programs on one single-wave workgroup. Test infrastructure only: built beside libovhip.so with
+// primitives of csrc/bls/fp.hpp and csrc/fpvm.hpp, one thread per case, a runner for Fp-VM
+// programs on one single-wave workgroup, and hash_to_field in the shape of the product's k_h2f
+// (tests/test_gpu_h2c.py). Test infrastructure only: built beside libovhip.so with
 // the product's flags (the product's code generation is what is under test), never linked into it.
 //
 // Every entry point takes host arrays (12 words per value), copies them to the device, launches
@@ -11,6 +12,7 @@
 
 #include <vector>
 
+#include "../../consensus_overlord_amd/csrc/bls/h2c.hpp"
 #include "../../consensus_overlord_amd/csrc/fpvm.hpp"
 
 using namespace ovh;
@@ -113,6 +115,26 @@ __global__ __launch_bounds__(64) void k_fp_inv(uint32_t n, const uint32_t* __res
   ld12(k, r3, 0);
   vm::fp_inv(z, x, k);
   st12(r, i, z);
+}
+
+// The shape of the product's k_h2f (csrc/ovhip.hip): the DST's templates by value in the kernel
+// arguments, indexed by a run-time block number; one lane per 32-byte message; u0.c0, u0.c1,
+// u1.c0, u1.c1 stored as hash_to_field leaves them (Montgomery limbs, 4 x 12 words per message).
+__global__ __launch_bounds__(64) void k_h2f_probe(uint32_t n, const uint8_t* __restrict__ hashes, XmdTemplates t,
+                                                  uint32_t* __restrict__ out) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  uint32_t msg[8], uni[64];
+  const uint8_t* b = hashes + (size_t)i * 32;
+  for (int w = 0; w < 8; ++w)
+    msg[w] = ((uint32_t)b[4 * w] << 24) | ((uint32_t)b[4 * w + 1] << 16) | ((uint32_t)b[4 * w + 2] << 8) | b[4 * w + 3];
+  expand_message_xmd_256(uni, msg, t);
+  Fp2 u0, u1;
+  hash_to_field_fp2x2(u0, u1, uni);
+  st12(out, i * 4 + 0, u0.c0);
+  st12(out, i * 4 + 1, u0.c1);
+  st12(out, i * 4 + 2, u1.c0);
+  st12(out, i * 4 + 3, u1.c1);
 }
 
 // LDS layout of the product's VM kernels (csrc/ovhip.hip): the constant table, then the slot
@@ -277,6 +299,24 @@ int dp_fp_inv(uint32_t n, const uint32_t* a, const uint32_t* r3, uint32_t* r) {
   k_fp_inv<<<grid(n), 64>>>(n, da, d3, dr);
   m.sync();
   m.down(r, dr, n * FPB);
+  return (int)m.err;
+}
+
+// The device counterpart of hx_h2f on n messages (msgs: n x 32 bytes) under one DST: out takes
+// n x 4 values (u0.c0, u0.c1, u1.c0, u1.c1), nb the templates' block counts {nb0, nbi}. A DST
+// that xmd_build_templates refuses (more than 255 bytes) returns an error without a launch.
+int dp_h2f(uint32_t n, const uint8_t* msgs, const uint8_t* dst, size_t dst_len, uint32_t* out, uint32_t* nb) {
+  if (n == 0 || n > (1u << 20) || !msgs || !out) return BAD;
+  XmdTemplates t;
+  if (!xmd_build_templates(t, dst, dst_len)) return BAD;
+  if (nb) nb[0] = t.nb0, nb[1] = t.nbi;
+  Bufs m;
+  const uint8_t* dm = m.up(msgs, (size_t)n * 32);
+  uint32_t* dr = m.up<uint32_t>(nullptr, (size_t)n * 4 * FPB);
+  if (m.err != hipSuccess) return (int)m.err;
+  k_h2f_probe<<<grid(n), 64>>>(n, dm, t, dr);
+  m.sync();
+  m.down(out, dr, (size_t)n * 4 * FPB);
   return (int)m.err;
 }
 

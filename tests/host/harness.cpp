@@ -20,7 +20,7 @@ void hx_vote_digest(uint8_t* out32, uint64_t h, uint64_t r, uint8_t t, const uin
   vote_digest(out32, h, r, t, bh, bl);
 }
 
-int hx_hash_to_g2(const uint8_t* msg32, const uint8_t* dst, uint32_t dst_len, uint8_t* out192) {
+int hx_hash_to_g2(const uint8_t* msg32, const uint8_t* dst, size_t dst_len, uint8_t* out192) {
   XmdTemplates t;
   if (!xmd_build_templates(t, dst, dst_len)) return -1;
   uint32_t m[8];
@@ -29,6 +29,36 @@ int hx_hash_to_g2(const uint8_t* msg32, const uint8_t* dst, uint32_t dst_len, ui
   hash_to_g2(h, m, t);
   g2_serialize(out192, h);
   return 0;
+}
+
+// The field half of hash_to_G2 (what k_h2f runs per message): the DST's block templates,
+// expand_message_xmd and hash_to_field. out192 = u0.c0, u0.c1, u1.c0, u1.c1 as 48-byte BE
+// canonical values; nb = {nb0, nbi} of the templates. -1: the DST is refused.
+int hx_h2f(const uint8_t* msg32, const uint8_t* dst, size_t dst_len, uint8_t* out192, uint32_t* nb) {
+  XmdTemplates t;
+  if (!xmd_build_templates(t, dst, dst_len)) return -1;
+  uint32_t m[8], uni[64];
+  be_words_from_bytes(m, msg32, 8);
+  expand_message_xmd_256(uni, m, t);
+  Fp2 u0, u1;
+  hash_to_field_fp2x2(u0, u1, uni);
+  const Fp* c[4] = {&u0.c0, &u0.c1, &u1.c0, &u1.c1};
+  for (int i = 0; i < 4; ++i) fp_to_be48(out192 + 48 * i, *c[i]);
+  if (nb) nb[0] = t.nb0, nb[1] = t.nbi;
+  return 0;
+}
+
+// The curve half (h2c.hpp map2_to_g2) on field inputs given as hash_to_field gets them: in256 =
+// four 64-byte big-endian integers (u0.c0, u0.c1, u1.c0, u1.c1), each reduced modulo p by
+// fp_from_be64_words. out192 = the serialized point (0x40 || zeros for the identity).
+void hx_map2_to_g2(const uint8_t* in256, uint8_t* out192) {
+  uint32_t w[64];
+  be_words_from_bytes(w, in256, 64);
+  Fp2 u0, u1;
+  hash_to_field_fp2x2(u0, u1, w);
+  G2J h;
+  map2_to_g2(h, u0, u1);
+  g2_serialize(out192, h);
 }
 
 int hx_verify(const uint8_t* sig, uint32_t sl, const uint8_t* hash, uint32_t hl, const uint8_t* pk, uint32_t pl) {

@@ -20,7 +20,10 @@ def hx():
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", tmp,
                            os.path.join(ROOT, "tests", "host", "harness.cpp")])
     os.replace(tmp, out)
-    return ctypes.CDLL(out)
+    lib = ctypes.CDLL(out)
+    # the DST length is a size_t (lengths past 2^32 are part of tests/test_h2c_host.py)
+    lib.hx_hash_to_g2.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p]
+    return lib
 
 
 def test_gt_value(hx, golden):
