@@ -3290,6 +3290,37 @@ static void enqueue_final(ovh_ctx* c, hipStream_t st, Slab F, Slab S, uint32_t m
   k_vm_final<<<1, 64, LDS_FINAL, st>>>(m, c->vm_final, c->vm_consts, F, S, xS, d_res);
 }
 
+// The MSM's sort half (msm.hpp): the counting sort of the votes' point ids by bucket, from the
+// RLC digits of the votes with code 0 -> cnt, off, pf, ent of `a`.
+static void enqueue_msm_sort(hipStream_t st, const MsmArgs& a, uint32_t* cur, uint32_t n, uint64_t seed, uint64_t base,
+                             const int32_t* d_codes) {
+  k_msm_zero<<<(MSM_NB + MSM_TPB - 1) / MSM_TPB, MSM_TPB, 0, st>>>((uint32_t*)a.cnt);  // (one-wave workgroups)
+  const uint32_t nb = (n + MSM_TPB - 1) / MSM_TPB;
+  k_msm_count<<<nb, MSM_TPB, 0, st>>>(n, seed, base, d_codes, (uint32_t*)a.cnt);
+  k_msm_scan<<<1, 64, 0, st>>>(a.cnt, (uint32_t*)a.off, cur, (uint32_t*)a.pf);
+  k_msm_scatter<<<nb, MSM_TPB, 0, st>>>(n, seed, base, d_codes, cur, (uint32_t*)a.ent);
+}
+
+// The MSM's tree half (msm.hpp): bucket sums, bit-plane sums and the window combination over the
+// sorted entries of `a` (at most 2n in a bucket, 8n in all) -> a.U[0].
+static void enqueue_msm_trees(ovh_ctx* c, hipStream_t st, const MsmArgs& a, uint32_t n, bool comb = true) {
+  // Every VM kernel below runs several tree levels inside one-wave workgroups that own what they
+  // touch (msm.hpp): six launches where each level used to be one (25 at 4,096 votes).
+  // bucket trees: levels 0-5 per 64-entry chunk of a bucket (<= 8n / 64 + NB chunks), then the
+  // levels above per bucket (no bucket has them up to 32 votes)
+  k_msm_chunk<<<(uint32_t)((8ull * n >> MSM_CH_LV) + MSM_NB), 64, LDS_MSM8, st>>>(c->vm_madd, c->vm_padd, MSM8_STRIDE_W,
+                                                                                   c->vm_consts, a);
+  if (2ull * n > MSM_CH) k_msm_upper<<<MSM_NB, 64, LDS_MSM8, st>>>(c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
+  // bit-plane sums T_t (128 buckets each): levels 0-3 per 16 buckets, then 4-6 per target
+  k_msm_plane<<<MSM_NT * (MSM_TM >> 3), 64, LDS_MSM8, st>>>(0, 3, c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
+  k_msm_plane<<<MSM_NT, 64, LDS_MSM8, st>>>(4, 6, c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
+  if (!comb) return;  // (tests/device/msm_probe.hip reads the T_t before they are combined)
+  // sum_t 2^t T_t: five levels of A + [2^m] B, m = 1, 2, 4 (per 8 targets), then 8, 16
+  k_msm_comb<<<MSM_NT >> 3, 64, LDS_HDBL, st>>>(1, 3, c->vm_hdbl[0], c->vm_hdbl[1], c->vm_hdbl[2], HDBL_STRIDE_W,
+                                                c->vm_consts, a);
+  k_msm_comb<<<1, 64, LDS_HDBL, st>>>(4, 5, c->vm_hdbl[3], c->vm_hdbl[4], c->vm_hdbl[4], HDBL_STRIDE_W, c->vm_consts, a);
+}
+
 // Pippenger MSM of the batch in `slot` on stream st (msm.hpp): S = sum of r_i sigma_i over the
 // votes with code 0 -> msm_S(c, slot). Needs the vote kernel's codes and sigma / tau planes.
 static int enqueue_msm(ovh_ctx* c, hipStream_t st, int slot, uint32_t n, const int32_t* d_codes) {
@@ -3302,25 +3333,8 @@ static int enqueue_msm(ovh_ctx* c, hipStream_t st, int slot, uint32_t n, const i
     return hipGetLastError() == hipSuccess ? 0 : OVH_ERR_DEVICE;
   }
   if (2ull * n > (1ull << MSM_LV)) return OVH_ERR_ARG;  // a bucket holds up to 2n points: MSM_LV tree levels
-  k_msm_zero<<<(MSM_NB + MSM_TPB - 1) / MSM_TPB, MSM_TPB, 0, st>>>((uint32_t*)a.cnt);  // (one-wave workgroups)
-  const uint32_t nb = (n + MSM_TPB - 1) / MSM_TPB;
-  k_msm_count<<<nb, MSM_TPB, 0, st>>>(n, seed, base, d_codes, (uint32_t*)a.cnt);
-  k_msm_scan<<<1, 64, 0, st>>>(a.cnt, (uint32_t*)a.off, cur, (uint32_t*)a.pf);
-  k_msm_scatter<<<nb, MSM_TPB, 0, st>>>(n, seed, base, d_codes, cur, (uint32_t*)a.ent);
-  // Every VM kernel below runs several tree levels inside one-wave workgroups that own what they
-  // touch (msm.hpp): six launches where each level used to be one (25 at 4,096 votes).
-  // bucket trees: levels 0-5 per 64-entry chunk of a bucket (<= 8n / 64 + NB chunks), then the
-  // levels above per bucket (no bucket has them up to 32 votes)
-  k_msm_chunk<<<(uint32_t)((8ull * n >> MSM_CH_LV) + MSM_NB), 64, LDS_MSM8, st>>>(c->vm_madd, c->vm_padd, MSM8_STRIDE_W,
-                                                                                   c->vm_consts, a);
-  if (2ull * n > MSM_CH) k_msm_upper<<<MSM_NB, 64, LDS_MSM8, st>>>(c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
-  // bit-plane sums T_t (128 buckets each): levels 0-3 per 16 buckets, then 4-6 per target
-  k_msm_plane<<<MSM_NT * (MSM_TM >> 3), 64, LDS_MSM8, st>>>(0, 3, c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
-  k_msm_plane<<<MSM_NT, 64, LDS_MSM8, st>>>(4, 6, c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
-  // sum_t 2^t T_t: five levels of A + [2^m] B, m = 1, 2, 4 (per 8 targets), then 8, 16
-  k_msm_comb<<<MSM_NT >> 3, 64, LDS_HDBL, st>>>(1, 3, c->vm_hdbl[0], c->vm_hdbl[1], c->vm_hdbl[2], HDBL_STRIDE_W,
-                                                c->vm_consts, a);
-  k_msm_comb<<<1, 64, LDS_HDBL, st>>>(4, 5, c->vm_hdbl[3], c->vm_hdbl[4], c->vm_hdbl[4], HDBL_STRIDE_W, c->vm_consts, a);
+  enqueue_msm_sort(st, a, cur, n, seed, base, d_codes);
+  enqueue_msm_trees(c, st, a, n);
   return hipGetLastError() == hipSuccess ? 0 : OVH_ERR_DEVICE;
 }
 
@@ -5991,6 +6005,9 @@ int ovh_build_qcs(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* hash
 
 int ovh_set_test_rlc(ovh_ctx* c, uint64_t seed, uint64_t index_base) {
   if (!c || !(c->flags & OVH_FLAG_TEST_RLC)) return OVH_ERR_ARG;
+  // the batch and shard paths add vote offsets to the base: one below 2^63 never reaches
+  // UNIT_BASE, which vote_scalar reads as "scalar 1"
+  if (index_base >> 63) return OVH_ERR_ARG;
   for (ovh_ctx* s : c->sub) {
     std::lock_guard<std::mutex> g(s->mu);
     s->test_seed = seed;

@@ -301,7 +301,9 @@ int ovh_build_qcs(ovh_ctx* ctx, size_t n, const uint8_t* sigs /* n x 96 */, cons
 /* TESTS ONLY (context created with OVH_FLAG_TEST_RLC, else OVH_ERR_ARG): vote i of every
  * following batch gets the coefficient SplitMix64(seed, index_base + i). Predictable
  * coefficients let an adversary cancel invalid signatures inside the combined check
- * (tests/test_rlc_soundness.py); production contexts never use this. */
+ * (tests/test_rlc_soundness.py); production contexts never use this. index_base must be below
+ * 2^63 (else OVH_ERR_ARG): the batch and shard paths add vote offsets to it, and the index
+ * 2^64 - 1 is reserved for the unit scalar of a single vote checked alone. */
 int ovh_set_test_rlc(ovh_ctx* ctx, uint64_t seed, uint64_t index_base);
 
 /* The same as ovh_verify_batch with device-resident inputs/outputs (pointers into HBM), enqueued

@@ -8,7 +8,10 @@ MSM's S) must pass or fail the combined check prod f * e(-G1, S) == 1 exactly as
 demand -- with every counted vote valid it passes only if S is exact, whatever the bisection
 would repair afterwards. The RLC digits spread evenly, so below ~6,000 votes no bucket has more
 than one 64-entry chunk; the 8,192-vote case is the one that runs chunks 1.. and k_msm_upper
-(tests/test_msm_chunk_model.py walks those paths on the CPU with crowded buckets)."""
+(tests/test_msm_chunk_model.py walks those paths on the CPU with crowded buckets, and
+tests/test_gpu_msm_buckets.py runs the kernels on crafted buckets against exact sums). The
+replayed votes are what a Byzantine validator can send: one vote many times puts identical points
+into every bucket, and sigma beside -sigma makes buckets cancel."""
 import os
 import random
 
@@ -117,6 +120,37 @@ def test_failed_votes_are_skipped(plain, fixed, votes, golden, n):
         codes, pcodes, verdict = _run(cc, sigs, hs, pks)
         assert codes.tolist() == want.tolist() and pcodes.tolist() == want.tolist()
         assert verdict, "S of the MSM is not the sum over the votes with code 0"
+
+
+REPLAYS = (2, 33, 65, 257)
+
+
+@pytest.mark.parametrize("n", REPLAYS)
+def test_one_vote_replayed(plain, fixed, votes, n):
+    """a validator's vote sent n times: every bucket's points are copies of sigma (or of tau), so
+    every pair add of the bucket trees is a doubling; all copies are valid and S is exact"""
+    sigs, hs, pks = (np.repeat(x[7:8], n, axis=0) for x in votes)
+    for cc in (plain, fixed):
+        codes, pcodes, verdict = _run(cc, sigs, hs, pks)
+        assert (codes == 0).all() and (pcodes == 0).all()
+        assert verdict, "S of the MSM is not (sum r_i) sigma"
+
+
+@pytest.mark.parametrize("n", REPLAYS)
+def test_one_vote_replayed_with_negated_copies(plain, fixed, votes, n):
+    """the same, with -sigma in the odd copies: buckets hold sigma and -sigma and cancel. The
+    negated copies fail as the oracle says; the partial counts every copy (a vote's code is 0
+    before any pairing), so its combined check fails"""
+    import bls12_381 as bls
+    sigs, hs, pks = (np.repeat(x[7:8], n, axis=0) for x in votes)
+    neg = bls.g2_compress(bls.pt_neg(bls.Fp2Ops, bls.g2_from_bytes(bytes(sigs[0]))))
+    sigs[1::2] = np.frombuffer(neg, dtype=np.uint8)
+    want = sv.oracle_codes(sigs, hs, pks)
+    assert want.tolist() == [5 * (k & 1) for k in range(n)]
+    for cc in (plain, fixed):
+        codes, pcodes, verdict = _run(cc, sigs, hs, pks)
+        assert codes.tolist() == want.tolist()
+        assert (pcodes == 0).all() and not verdict
 
 
 def test_buckets_of_several_chunks(fixed):
