@@ -302,6 +302,35 @@ class ConsensusCrypto:
         n, sig, hs, pk = self._fixed(signatures, hashes, voters)
         raise_for(self.lib.ovh_prefetch(self.ctx.ptr, n, sig, hs, pk))
 
+    PRIME_MAX = 64   # include/ovhip.h OVH_PRIME_MAX
+
+    def prime(self, hashes) -> None:
+        """Prime H(m) of 32-byte hashes this node is about to sign or verify (ovh_prime_hashes):
+        hash_to_G2 of every hash not yet in the message cache is enqueued on a side stream and
+        the call returns without waiting for the device. The first verify_signature on a primed
+        hash, sign on it and a small verify_batch / prefetch whose hashes are all primed then
+        skip hash_to_G2. Call it at proposal receipt (prevote and precommit hashes of the
+        block), at round start (the nil votes and the choke) and on the first vote of a group."""
+        hs = [bytes(h) for h in hashes]
+        if any(len(h) != 32 for h in hs):
+            raise ValueError("32-byte hashes")
+        for k in range(0, len(hs), self.PRIME_MAX):
+            chunk = hs[k:k + self.PRIME_MAX]
+            raise_for(self.lib.ovh_prime_hashes(self.ctx.ptr, len(chunk), b"".join(chunk)))
+
+    def prime_votes(self, votes) -> None:
+        """prime() of hash(rlp(Vote)) for (height, round, vote_type, block_hash) tuples: the host
+        SM3 of about 50 bytes each (no device round trip before the prime)."""
+        from . import vote as _vote
+        self.prime([self.hash(_vote.rlp_vote(h, r, t, bytes(bh))) for h, r, t, bh in votes])
+
+    def prime_stats(self):
+        """(hashes enqueued, hashes skipped as cached or repeated, signs served from the cache,
+        small-batch parts run on cached H) since the context was created (ovh_prime_stats)."""
+        st = (ctypes.c_uint64 * 4)()
+        raise_for(self.lib.ovh_prime_stats(self.ctx.ptr, st))
+        return tuple(int(x) for x in st)
+
     def cache_stats(self):
         """(hits, misses, entries) of the verdict cache."""
         st = (ctypes.c_uint64 * 3)()

@@ -1157,6 +1157,59 @@ __global__ __launch_bounds__(64) void k_vm_votew(uint32_t n, VmDev prog, const u
                      pk, e, sigs + (size_t)i * 96, s, i, vote_scalar(seed, base, i), codes + i);
 }
 
+// A small batch on hashes in the message cache (ovh_prime_hashes): k_vm_votew with H of vote i
+// from cache entry hent[i] (programs votewh / votewh_t: no hash_to_G2, no u planes) and the
+// H = O flag from hinf, as vote1h reads it.
+static_assert(VM_VOTEWH_NIN == VM_VOTE1H_NIN && VM_VOTEWH_T_NIN == VM_VOTE_T1H_NIN && VM_VOTEWH_W == 64 &&
+                  VM_VOTEWH_T_W == 64 && VM_VOTEWH_IN_H0 == VM_VOTE1H_IN_H0 && VM_VOTEWH_T_IN_H0 == VM_VOTE_T1H_IN_H0 &&
+                  VM_VOTEWH_OUT_SIG_GRP == VM_VOTE1H_OUT_SIG_GRP && VM_VOTEWH_T_OUT_SIG_GRP == VM_VOTE_T1H_OUT_SIG_GRP,
+              "votewh / votewh_t share vote1h / vote_t1h's layouts");
+template <bool TABLE>
+__global__ __launch_bounds__(64) void k_vm_votewh(uint32_t n, VmDev prog, const uint32_t* __restrict__ cst_g,
+                                                  const uint8_t* __restrict__ pks, PkSrc pk,
+                                                  const uint8_t* __restrict__ sigs, Slab s, uint64_t seed,
+                                                  uint64_t base, int32_t* __restrict__ codes, Slab hc,
+                                                  const uint32_t* __restrict__ hent,
+                                                  const uint32_t* __restrict__ hinf) {
+  const uint32_t i = blockIdx.x;
+  if (i >= n) return;
+  const uint32_t e = TABLE ? (pk.idx ? (uint32_t)pk.idx[i] : i) : 0u;
+  const uint32_t he = hent[i] < hc.cap ? hent[i] : 0u;
+  if constexpr (TABLE)
+    vote_wave<true, true>(prog, VM_VOTEWH_T_NPHASES, VM_VOTEWH_T_NSLOTS, VM_VOTEWH_T_IN, VM_VOTEWH_T_OUT, cst_g, nullptr,
+                          pk, e, sigs + (size_t)i * 96, s, i, vote_scalar(seed, base, i), codes + i, hc, he, hinf + he);
+  else
+    vote_wave<false, true>(prog, VM_VOTEWH_NPHASES, VM_VOTEWH_NSLOTS, VM_VOTEWH_IN, VM_VOTEWH_OUT, cst_g,
+                           pks + (size_t)i * 48, pk, e, sigs + (size_t)i * 96, s, i, vote_scalar(seed, base, i),
+                           codes + i, hc, he, hinf + he);
+}
+
+// ovh_prime_hashes: the hashes and the cache entries chosen for them travel as kernel arguments,
+// so no host buffer has to outlive the call and nothing is copied from pageable memory.
+struct PrimeHashes {
+  uint8_t b[OVH_PRIME_MAX * 32];
+};
+struct PrimeEnts {
+  uint16_t e[OVH_PRIME_MAX];
+};
+__global__ __launch_bounds__(64) void k_prime_put(uint32_t k, PrimeHashes h, uint8_t* __restrict__ out) {
+  if (k > OVH_PRIME_MAX) return;
+  for (uint32_t j = threadIdx.x; j < k * 32; j += 64) out[j] = h.b[j];
+}
+// H planes and the H = O flag of prime-slab group q -> message-cache entry ent.e[q] (k_copy_h for
+// a list of entries): workgroup q.
+__global__ __launch_bounds__(64) void k_prime_scatter(uint32_t k, PrimeEnts ent, Slab g,
+                                                      const uint32_t* __restrict__ ghinf, Slab hc,
+                                                      uint32_t* __restrict__ hc_inf) {
+  const uint32_t q = blockIdx.x;
+  if (q >= k || q >= OVH_PRIME_MAX || q >= g.cap) return;
+  const uint32_t he = ent.e[q];
+  if (he >= hc.cap) return;
+  for (uint32_t w = threadIdx.x; w < 6 * 12; w += 64)
+    hc.p[(size_t)w * hc.cap + he] = g.p[(size_t)(VM_G_H * 12 + w) * g.cap + q];
+  if (threadIdx.x == 0) hc_inf[he] = ghinf[q];
+}
+
 // ------------------------------------------------------------------ same-message batches (r04)
 // A round's votes all sign one hash (consensus.rs:169-175: Vote carries no voter), so a batch of
 // n votes over G distinct hashes is checked as
@@ -1929,15 +1982,24 @@ __device__ __forceinline__ uint64_t signg_scalar(const uint64_t d[4], int j) {
   return v;
 }
 
-constexpr uint32_t SIGNG_NSLOTS = VM_SIGNG0_NSLOTS > VM_SIGNG1_NSLOTS ? VM_SIGNG0_NSLOTS : VM_SIGNG1_NSLOTS;
+constexpr uint32_t SIGNG_NSLOTS = VM_SIGNG0_NSLOTS > VM_SIGNG1_NSLOTS
+                                      ? (VM_SIGNG0_NSLOTS > VM_SIGNG0H_NSLOTS ? VM_SIGNG0_NSLOTS : VM_SIGNG0H_NSLOTS)
+                                      : (VM_SIGNG1_NSLOTS > VM_SIGNG0H_NSLOTS ? VM_SIGNG1_NSLOTS : VM_SIGNG0H_NSLOTS);
 constexpr uint32_t SIGNG_STRIDE_W = align256w(SIGNG_NSLOTS * 12 + 96 * 12 + 8);  // + acc, T stash, digits
 // bl: a uniform random nonzero Fp2 blinding factor per signature (planes 0, 1; host getrandom),
-// multiplied into (X : Y : Z) before the one-lane compression inverts Z (as k_vm_pkgen)
+// multiplied into (X : Y : Z) before the one-lane compression inverts Z (as k_vm_pkgen).
+// hc.p set (ovh_sign on a hash in the message cache): p0 is signg0h, every signature's H comes
+// from cache entry he and the u planes are not read. The flag is a launch argument, not a
+// template parameter: the one branch (which inputs to load) is wave-uniform, the interpreter is
+// bound once either way, and the kernel keeps its one instantiation (its code size is held by
+// tests/test_code_size.py).
 __global__ __launch_bounds__(64) void k_vm_signg(uint32_t n, VmDev p0, VmDev p1, const uint32_t* __restrict__ cst_g,
                                                  const uint8_t* __restrict__ sks, Slab s, uint8_t* __restrict__ out,
-                                                 Slab bl) {
-  static_assert(VM_SIGNG0_W == VM_SIGNG1_W && VM_SIGNG0_NOUT == 96 && VM_SIGNG1_NIN == 96 && VM_SIGNG1_NOUT == 6,
+                                                 Slab bl, Slab hc, uint32_t he) {
+  static_assert(VM_SIGNG0_W == VM_SIGNG1_W && VM_SIGNG0_NOUT == 96 && VM_SIGNG1_NIN == 96 && VM_SIGNG1_NOUT == 6 &&
+                    VM_SIGNG0H_W == VM_SIGNG0_W && VM_SIGNG0H_NOUT == 96 && VM_SIGNG0H_NIN == 6,
                 "signg program shapes (tools/fpvm/progs.py)");
+  const bool htab = hc.p != nullptr;
   constexpr uint32_t W = VM_SIGNG0_W;
   extern __shared__ uint4 lds4[];
   uint32_t* lds = reinterpret_cast<uint32_t*>(lds4);
@@ -1959,10 +2021,14 @@ __global__ __launch_bounds__(64) void k_vm_signg(uint32_t n, VmDev p0, VmDev p1,
       for (int j = 0; j < 4; ++j) dig[j] = d[j];
       k[0] = k[1] = k[2] = k[3] = 0;
       d[0] = d[1] = d[2] = d[3] = 0;
-    } else if (lane >= 1 && lane < 5) {
+    } else if (!htab && lane >= 1 && lane < 5) {
       Fp u;
       s.ld(u, S_U + (lane - 1), i);
       slot_put(slots, VM_SIGNG0_IN[lane - 1], u.v);
+    } else if (htab && lane >= 1 && lane < 7) {
+      Fp h;
+      hc.ld(h, lane - 1, he);
+      slot_put(slots, VM_SIGNG0H_IN[lane - 1], h.v);
     }
   }
   __syncthreads();
@@ -1971,12 +2037,16 @@ __global__ __launch_bounds__(64) void k_vm_signg(uint32_t n, VmDev p0, VmDev p1,
     for (int j = 0; j < 4; ++j) d[j] = dig[j];
   VM_ASSERT_NO_INV(SIGNG0);
   VM_ASSERT_NO_INV(SIGNG1);
-  vm::run<false, false>(p0.code, VM_SIGNG0_NPHASES, W, lane, active, slots, cst, signg_scalar(d, 0),
-                        vm::Out{nullptr, 0, 0});
+  VM_ASSERT_NO_INV(SIGNG0H);
+  // p0's phase count and output map come with the program (VmDev), so nothing of the choice
+  // between signg0 and signg0h stays live across the run
+  vm::run<false, false>(p0.code, p0.nphases, W, lane, active, slots, cst, signg_scalar(d, 0), vm::Out{nullptr, 0, 0});
   __syncthreads();
   if (active)
-    for (uint32_t q = lane; q < 96; q += W)
-      for (int l = 0; l < 12; ++l) hst[q * 12 + l] = slots[VM_SIGNG0_OUT[q] * 12 + l];
+    for (uint32_t q = lane; q < 96; q += W) {
+      const uint32_t o = p0.out[q];
+      for (int l = 0; l < 12; ++l) hst[q * 12 + l] = slots[o * 12 + l];
+    }
   __syncthreads();
   for (int r = 1; r < 4; ++r) {
     if (active)
@@ -2601,6 +2671,19 @@ struct ovh_ctx {
   std::vector<std::string> hc_keys;
   uint32_t hc_next = 0;
   uint64_t hc_hits = 0, hc_misses = 0;
+  // ovh_prime_hashes: the side stream (normal priority; lazy), the prime path's group slab
+  // (OVH_PRIME_MAX entries of VM_G_PLANES planes, the H = O words and the hash bytes behind
+  // them), the event recorded on `stream` at each call, and the event of the last prime with
+  // whether a cache user has yet to wait for it (hc_touch)
+  hipStream_t prime_st = nullptr;
+  uint32_t* prime_slab = nullptr;
+  hipEvent_t prime_ev0 = nullptr, prime_ev = nullptr;
+  bool prime_pending = false;
+  uint64_t prime_enq = 0, prime_skip = 0, prime_signs = 0, prime_parts = 0;
+  // consumers of the cache beside the per-call verify (OVH_PRIME_SIGN / OVH_PRIME_BATCH, read
+  // at ovh_create)
+  bool prime_sign = true, prime_batch = true;
+  VmDev vm_votewh{}, vm_votewh_t{}, vm_signg0h{};
   uint32_t* vm_consts = nullptr;
   std::vector<void*> vm_bufs;
   uint32_t clk_wgs = 0;    // OVH_FLAG_VM_CLOCK: workgroups of the last vote launch
@@ -2654,6 +2737,12 @@ static constexpr uint32_t VOTE1H_NSLOTS = VM_VOTE1H_NSLOTS > VM_VOTE_T1H_NSLOTS 
 static constexpr size_t LDS_VOTE1H = ((size_t)SLOT_BASE_W + VOTE1H_NSLOTS * 12 + 4) * 4;
 static constexpr uint32_t VOTEW_NSLOTS = VM_VOTEW_NSLOTS > VM_VOTEW_T_NSLOTS ? VM_VOTEW_NSLOTS : VM_VOTEW_T_NSLOTS;
 static constexpr size_t LDS_VOTEW = ((size_t)SLOT_BASE_W + VOTEW_NSLOTS * 12 + 4) * 4;
+// votewh / votewh_t hold the key side and the signature side at once (no hash_to_G2 to run the
+// signature's half beside): a larger slot file than votew's, so fewer workgroups per CU. A part
+// goes to k_vm_votewh only if its waves are co-resident (one round of the 256 CUs), as votew's
+// are for every small batch: VOTEWH_MAX votes.
+static constexpr uint32_t VOTEWH_NSLOTS = VM_VOTEWH_NSLOTS > VM_VOTEWH_T_NSLOTS ? VM_VOTEWH_NSLOTS : VM_VOTEWH_T_NSLOTS;
+static constexpr size_t LDS_VOTEWH = ((size_t)SLOT_BASE_W + VOTEWH_NSLOTS * 12 + 4) * 4;
 static constexpr size_t LDS_QCPRE = ((size_t)SLOT_BASE_W + VM_QCPRE_NSLOTS * 12 + 4) * 4;
 static constexpr size_t LDS_QCMIL = ((size_t)SLOT_BASE_W + VM_QCMIL_NSLOTS * 12) * 4;
 static constexpr size_t LDS_FINAL1 = ((size_t)SLOT_BASE_W + (size_t)VM_FINAL1_NSLOTS * 12) * 4;
@@ -2687,6 +2776,10 @@ constexpr size_t lds_granule(size_t b) { return (b + 1023) / 1024 * 1024; }
 // the vote pool: eight workgroups per CU (constants + four slices of the larger slot file)
 static constexpr size_t LDS_POOL = LDS_VOTE > LDS_VOTE_T ? LDS_VOTE : LDS_VOTE_T;
 static_assert(8 * lds_granule(LDS_POOL) <= 160 * 1024, "eight pool workgroups per CU");
+static_assert(4 * lds_granule(LDS_VOTEW) <= 160 * 1024, "four votew workgroups per CU: a small batch is one round");
+static constexpr uint32_t VOTEWH_PER_CU = (uint32_t)(160 * 1024 / lds_granule(LDS_VOTEWH));
+static constexpr uint32_t VOTEWH_MAX = 256 * VOTEWH_PER_CU < SMALL_MAX ? 256 * VOTEWH_PER_CU : SMALL_MAX;
+static_assert(LDS_VOTEWH <= 64 * 1024 && VOTEWH_PER_CU >= 4, "votewh LDS (default limit; four per CU: 1,024 waves)");
 static_assert(VOTE_NSCR <= 4096 && VM_VOTE_NSLOTS <= 2048 && VM_VOTE_T_NSLOTS <= 2048,
               "side words: 12-bit scratch entries, 11-bit slots (fpvm.hpp side_spill)");
 // pool workgroups left out per eight CUs (their places hold the final streams' kernels and
@@ -2801,6 +2894,12 @@ static int vm_init(ovh_ctx* c) {
                 VM_VOTEW_OUT, VM_VOTEW_NOUT));
   CHK(vm_upload(c, c->vm_votew_t, VM_VOTEW_T_CODE, VM_VOTEW_T_NPHASES, VM_VOTEW_T_W, VM_VOTEW_T_NW, VM_VOTEW_T_IN,
                 VM_VOTEW_T_NIN, VM_VOTEW_T_OUT, VM_VOTEW_T_NOUT));
+  CHK(vm_upload(c, c->vm_votewh, VM_VOTEWH_CODE, VM_VOTEWH_NPHASES, VM_VOTEWH_W, VM_VOTEWH_NW, VM_VOTEWH_IN, VM_VOTEWH_NIN,
+                VM_VOTEWH_OUT, VM_VOTEWH_NOUT));
+  CHK(vm_upload(c, c->vm_votewh_t, VM_VOTEWH_T_CODE, VM_VOTEWH_T_NPHASES, VM_VOTEWH_T_W, VM_VOTEWH_T_NW, VM_VOTEWH_T_IN,
+                VM_VOTEWH_T_NIN, VM_VOTEWH_T_OUT, VM_VOTEWH_T_NOUT));
+  CHK(vm_upload(c, c->vm_signg0h, VM_SIGNG0H_CODE, VM_SIGNG0H_NPHASES, VM_SIGNG0H_W, VM_SIGNG0H_NW, VM_SIGNG0H_IN,
+                VM_SIGNG0H_NIN, VM_SIGNG0H_OUT, VM_SIGNG0H_NOUT));
   CHK(vm_upload(c, c->vm_final1, VM_FINAL1_CODE, VM_FINAL1_NPHASES, VM_FINAL1_W, VM_FINAL1_NW, VM_FINAL1_IN,
                 VM_FINAL1_NIN, VM_FINAL1_OUT, VM_FINAL1_NOUT));
   CHK(vm_upload(c, c->vm_vsame, VM_VSAME_CODE, VM_VSAME_NPHASES, VM_VSAME_W, VM_VSAME_NW, VM_VSAME_IN, VM_VSAME_NIN,
@@ -3383,13 +3482,106 @@ static int side_front(ovh_ctx* c, int slot, uint32_t until, int* reg, uint32_t* 
   return fold_down(c, slot, fst, 1, reg, m, until);
 }
 
+// ---- the message table: H = hash_to_G2(hash) of the last HC_CAP hashes (projective planes and
+// the H = O flag per entry, FIFO replacement), keyed by the 32 hash bytes on the host. A service
+// of the context: the per-call verify (verify_one_locked) looks up and inserts, ovh_prime_hashes
+// inserts ahead of use, ovh_sign and the small-batch route (verify_host_locked) only look up.
+// Every reader and the per-call insert run on c->stream; a prime fills its entries on
+// c->prime_st. Invariants:
+//  - an entry is registered in the host index (hc_register) only after every launch that fills
+//    it was accepted; hc_claim drops the old key before the planes are overwritten;
+//  - nothing reads an entry before its fill has completed on the device: fills on c->stream are
+//    in stream order, and hc_touch makes c->stream wait for the last prime before any lookup hit
+//    or insert is enqueued (work that does not touch the table never waits for a prime);
+//  - nothing overwrites an entry while a kernel enqueued earlier may still read it: the per-call
+//    insert is behind the readers in stream order, and a prime's scatter waits for an event
+//    recorded on c->stream at the time of the call;
+//  - hc_hits / hc_misses (ovh_msg_cache_stats) count the per-call verify's lookups only.
+#define HC_CAP 256u
+static int hc_ensure(ovh_ctx* c) {
+  if (c->hc_planes) return 0;
+  HIPCHK(hipMalloc(&c->hc_planes, (size_t)6 * 12 * HC_CAP * 4));
+  HIPCHK(hipMalloc(&c->hc_inf, (size_t)HC_CAP * 4));
+  c->hc_keys.assign(HC_CAP, std::string());
+  return 0;
+}
+static bool hc_find(const ovh_ctx* c, const std::string& hk, uint32_t* he) {
+  auto it = c->hc_index.find(hk);
+  if (it == c->hc_index.end()) return false;
+  *he = it->second;
+  return true;
+}
+// Before a lookup hit or an insert is enqueued on c->stream: the stream waits for the last prime.
+static int hc_touch(ovh_ctx* c) {
+  if (!c->prime_pending) return 0;
+  HIPCHK(hipStreamWaitEvent(c->stream, c->prime_ev, 0));
+  c->prime_pending = false;
+  return 0;
+}
+// The next entry in FIFO order, its old key dropped from the index.
+static uint32_t hc_claim(ovh_ctx* c) {
+  const uint32_t he = c->hc_next;
+  c->hc_next = (c->hc_next + 1) % HC_CAP;
+  if (!c->hc_keys[he].empty()) c->hc_index.erase(c->hc_keys[he]);
+  c->hc_keys[he].clear();
+  return he;
+}
+static void hc_register(ovh_ctx* c, uint32_t he, const std::string& hk) {
+  c->hc_keys[he] = hk;
+  c->hc_index[hk] = he;
+}
+
+// ovh_prime_hashes on one device (caller holds c->mu): hash_to_field and hash_to_G2 (k_vm_h2g,
+// four hashes per wave) of the hashes not in the table into the prime slab on c->prime_st, at
+// once; then, behind everything enqueued on c->stream so far (earlier readers of the entries
+// about to be replaced), the scatter into the claimed entries. No host synchronisation.
+static int prime_locked(ovh_ctx* c, size_t k, const uint8_t* hashes) {
+  HIPCHK(hipSetDevice(c->device));
+  CHK(hc_ensure(c));
+  PrimeHashes ph{};
+  PrimeEnts pe{};
+  std::vector<std::string> keys;
+  for (size_t i = 0; i < k; ++i) {
+    std::string hk((const char*)hashes + 32 * i, 32);
+    uint32_t he;
+    if (hc_find(c, hk, &he) || std::find(keys.begin(), keys.end(), hk) != keys.end()) continue;
+    memcpy(ph.b + 32 * keys.size(), hk.data(), 32);
+    keys.push_back(std::move(hk));
+  }
+  const uint32_t m = (uint32_t)keys.size();
+  c->prime_skip += k - m;
+  if (!m) return 0;
+  constexpr size_t SLAB_W = (size_t)VM_G_PLANES * 12 * OVH_PRIME_MAX;
+  if (!c->prime_st) HIPCHK(stream_new(&c->prime_st, 0));
+  if (!c->prime_slab) HIPCHK(hipMalloc(&c->prime_slab, (SLAB_W + OVH_PRIME_MAX + OVH_PRIME_MAX * 8) * 4));
+  for (hipEvent_t* e : {&c->prime_ev0, &c->prime_ev})
+    if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  const Slab g{c->prime_slab, OVH_PRIME_MAX};
+  uint32_t* ghinf = c->prime_slab + SLAB_W;
+  uint8_t* ghash = (uint8_t*)(ghinf + OVH_PRIME_MAX);
+  for (uint32_t j = 0; j < m; ++j) pe.e[j] = (uint16_t)hc_claim(c);
+  const hipStream_t ps = c->prime_st;
+  HIPCHK(hipEventRecord(c->prime_ev0, c->stream));
+  k_prime_put<<<1, 64, 0, ps>>>(m, ph, ghash);
+  k_h2f<<<nblk(m), WG, 0, ps>>>(m, ghash, c->xmd, g);
+  k_vm_h2g<<<(m + VM_SLICES - 1) / VM_SLICES, 64, LDS_H2G, ps>>>(m, c->vm_h2g, c->vm_consts, g, ghinf);
+  HIPCHK(hipStreamWaitEvent(ps, c->prime_ev0, 0));
+  k_prime_scatter<<<m, 64, 0, ps>>>(m, pe, g, ghinf, Slab{c->hc_planes, HC_CAP}, c->hc_inf);
+  // a failed launch leaves the claimed entries unregistered
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->prime_ev, ps));
+  c->prime_pending = true;
+  for (uint32_t j = 0; j < m; ++j) hc_register(c, pe.e[j], keys[j]);
+  c->prime_enq += m;
+  return 0;
+}
+
 // One standalone vote on the main stream (k_h2f, k_vm_vote1 / k_vm_vote_t1, k_vm_final1): its
 // own pairing equation, no coefficient (section 1 of DESIGN.md). Caller holds c->mu and waits.
-// h_host: the hash's host bytes, for the message cache (every vote of a round signs the same
-// hash): a hash seen before runs vote1h / vote_t1h on its cached H, without hash_to_G2 (vote1
-// 2,061 -> 1,444 phases); a new one runs vote1 / vote_t1, whose stored H is copied into the
-// cache (FIFO, HC_CAP entries). Null: no cache.
-#define HC_CAP 256u
+// h_host: the hash's host bytes, for the message table above (every vote of a round signs the
+// same hash): a hash in the table (seen before, or primed) runs vote1h / vote_t1h on its H,
+// without hash_to_G2 (vote1 2,061 -> 1,444 phases); a new one runs vote1 / vote_t1, whose stored
+// H is copied into the table. Null: no table.
 static int verify_one_locked(ovh_ctx* c, const uint8_t* d_sig, const uint8_t* d_hash, KeySrc key, int32_t* d_code,
                              const uint8_t* h_host = nullptr) {
   CHK(ensure_cap(c, 1));
@@ -3398,19 +3590,15 @@ static int verify_one_locked(ovh_ctx* c, const uint8_t* d_sig, const uint8_t* d_
   c->last_n = 0;  // no partial state for ovh_batch_partial_device / fallback
   Slab s{c->state_slot[slot], c->cap};
   hipStream_t st = c->stream;
-  if (h_host && !c->hc_planes) {
-    HIPCHK(hipMalloc(&c->hc_planes, (size_t)6 * 12 * HC_CAP * 4));
-    HIPCHK(hipMalloc(&c->hc_inf, (size_t)HC_CAP * 4));
-    c->hc_keys.assign(HC_CAP, std::string());
-  }
+  if (h_host) CHK(hc_ensure(c));
   const Slab hc{c->hc_planes, HC_CAP};
   std::string hk;
   if (h_host) {
     hk.assign((const char*)h_host, 32);
-    auto it = c->hc_index.find(hk);
-    if (it != c->hc_index.end()) {
+    uint32_t he;
+    if (hc_find(c, hk, &he)) {
       ++c->hc_hits;
-      const uint32_t he = it->second;
+      CHK(hc_touch(c));
       if (key.bytes)
         k_vm_vote1h<false><<<1, 64, LDS_VOTE1H, st>>>(c->vm_vote1h, c->vm_consts, key.bytes, PkSrc{}, d_sig, s, d_code,
                                                       hc, he, c->hc_inf);
@@ -3427,12 +3615,10 @@ static int verify_one_locked(ovh_ctx* c, const uint8_t* d_sig, const uint8_t* d_
   }
   uint32_t he = 0;
   if (h_host) {  // the entry is filled in stream order, before any later call can read it
-    he = c->hc_next;
-    c->hc_next = (c->hc_next + 1) % HC_CAP;
-    // the old entry's planes are about to be overwritten: drop it now; the new key is entered
+    CHK(hc_touch(c));
+    // the old entry's planes are about to be overwritten: dropped now; the new key is entered
     // only once every launch that fills the planes was accepted (below)
-    if (!c->hc_keys[he].empty()) c->hc_index.erase(c->hc_keys[he]);
-    c->hc_keys[he].clear();
+    he = hc_claim(c);
   }
   k_h2f<<<1, WG, 0, st>>>(1, d_hash, c->xmd, s);
   if (key.bytes)
@@ -3444,10 +3630,7 @@ static int verify_one_locked(ovh_ctx* c, const uint8_t* d_sig, const uint8_t* d_
   if (h_host) k_copy_h<<<1, 64, 0, st>>>(s, hc, he);
   // a failed launch of k_h2f / vote1 / k_copy_h leaves the entry unregistered
   HIPCHK(hipGetLastError());
-  if (h_host) {
-    c->hc_keys[he] = hk;
-    c->hc_index[hk] = he;
-  }
+  if (h_host) hc_register(c, he, hk);
   k_vm_final1<<<1, 64, LDS_FINAL1, st>>>(c->vm_final1, c->vm_consts, Slab{s.p + (size_t)S_F * 12 * s.cap, s.cap},
                                           d_code, c->result + RES_BATCH + slot);
   HIPCHK(hipEventRecord(c->ev_back[slot], st));
@@ -3461,8 +3644,10 @@ static int verify_one_locked(ovh_ctx* c, const uint8_t* d_sig, const uint8_t* d_
 // the votes with code 0 down to one partial, FE(prod f_i) == 1 (k_vm_fe) and, when that fails,
 // FE(f_i) == 1 per vote (k_vm_votefe). No MSM, no Miller loop in the final: one final
 // exponentiation per batch. Caller holds c->mu.
+// d_hent (the primed route, verify_host_locked): vote i's hash is message-table entry d_hent[i];
+// k_vm_votewh on the table's H in place of hash_to_field and k_vm_votew, the same tail.
 static int verify_small_locked(ovh_ctx* c, uint32_t n, const uint8_t* d_sigs, const uint8_t* d_hashes, KeySrc key,
-                               int32_t* d_codes) {
+                               int32_t* d_codes, const uint32_t* d_hent = nullptr) {
   int slot;
   CHK(take_slot(c, &slot));
   Slab s{c->state_slot[slot], c->cap};
@@ -3472,11 +3657,20 @@ static int verify_small_locked(ovh_ctx* c, uint32_t n, const uint8_t* d_sigs, co
   CHK(draw_seed(c, &seed, &base));
   c->slot_seed[slot] = seed;
   c->slot_base[slot] = base;
-  {
-    StageScope p(c, ST_H2F);
-    k_h2f<<<nblk(n), WG, 0, st>>>(n, d_hashes, c->xmd, s);
-  }
-  {
+  if (d_hent) {
+    StageScope p(c, ST_VOTE);
+    const Slab hc{c->hc_planes, HC_CAP};
+    if (key.bytes)
+      k_vm_votewh<false><<<n, 64, LDS_VOTEWH, st>>>(n, c->vm_votewh, c->vm_consts, key.bytes, PkSrc{}, d_sigs, s, seed,
+                                                    base, d_codes, hc, d_hent, c->hc_inf);
+    else
+      k_vm_votewh<true><<<n, 64, LDS_VOTEWH, st>>>(n, c->vm_votewh_t, c->vm_consts, nullptr, key.pts, d_sigs, s, seed,
+                                                   base, d_codes, hc, d_hent, c->hc_inf);
+  } else {
+    {
+      StageScope p(c, ST_H2F);
+      k_h2f<<<nblk(n), WG, 0, st>>>(n, d_hashes, c->xmd, s);
+    }
     StageScope p(c, ST_VOTE);
     if (key.bytes)
       k_vm_votew<false><<<n, 64, LDS_VOTEW, st>>>(n, c->vm_votew, c->vm_consts, key.bytes, PkSrc{}, d_sigs, s, seed,
@@ -3517,9 +3711,9 @@ static int verify_small_locked(ovh_ctx* c, uint32_t n, const uint8_t* d_sigs, co
 // (batch_front), then on the slot's final stream the fold levels, the MSM, the combined check and
 // the device-gated bisection. Nothing waits on the host. Caller holds c->mu.
 static int verify_async_locked(ovh_ctx* c, size_t n, const uint8_t* d_sigs, const uint8_t* d_hashes, KeySrc key,
-                               int32_t* d_codes) {
+                               int32_t* d_codes, const uint32_t* d_hent = nullptr) {
   CHK(ensure_cap(c, n));
-  if (n >= 2 && n <= c->small_max) return verify_small_locked(c, (uint32_t)n, d_sigs, d_hashes, key, d_codes);
+  if (n >= 2 && n <= c->small_max) return verify_small_locked(c, (uint32_t)n, d_sigs, d_hashes, key, d_codes, d_hent);
   int slot;
   CHK(pool_take_slot(c, &slot));
   CHK(batch_front(c, slot, (uint32_t)n, d_sigs, d_hashes, key, d_codes, true));
@@ -3860,7 +4054,9 @@ static int verify_host_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const u
     same = 2 * (size_t)pl.G <= n;
   }
   pl.off = (n * (96 + 32 + 48 + 4 + 4) + 255) / 256 * 256;
-  CHK(ensure_in(c, same ? pl.off + pl.bytes + 64 : n * (96 + 32 + 48 + 4 + 4) + 64));
+  // (behind the table indices: the message-table entries of a part on primed hashes)
+  CHK(ensure_in(c, same ? pl.off + pl.bytes + 64 : n * (96 + 32 + 48 + 4 + 4 + 4) + 64));
+  std::vector<uint32_t> hent;  // lives until sync_all below: the source of an asynchronous copy
   uint8_t* d;
   size_t t;
   CHK(stage_split(c, n, sigs, hashes, pks, &d, &t, perm));
@@ -3886,7 +4082,28 @@ static int verify_host_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const u
     for (int part = 0; part < 2; ++part) {  // table votes [0, t), then the others [t, n)
       const size_t lo = part ? t : 0, cnt = part ? n - t : t;
       if (!cnt) continue;
-      CHK(verify_async_locked(c, cnt, d + 96 * lo, d + n * 96 + 32 * lo, staged_key(c, n, d, t, lo), dc + lo));
+      // a part of 2 .. small_max votes whose hashes are all in the message table (ovh_prime_hashes,
+      // or seen by the per-call verify) runs k_vm_votewh on the table's H: no hash_to_field, no
+      // hash_to_G2 per vote. VOTEWH_MAX: its waves are co-resident. The entries travel in the
+      // staging image, in the votes' staged order.
+      const uint32_t* d_hent = nullptr;
+      if (c->prime_batch && c->hc_planes && cnt >= 2 && cnt <= c->small_max && cnt <= VOTEWH_MAX) {
+        hent.resize(n);
+        bool all = true;
+        std::string hk;
+        for (size_t j = lo; j < lo + cnt && all; ++j) {
+          hk.assign((const char*)hashes + 32 * (perm.empty() ? j : perm[j]), 32);
+          all = hc_find(c, hk, &hent[j]);
+        }
+        if (all) {
+          CHK(hc_touch(c));
+          uint32_t* dh = (uint32_t*)(d + n * 184) + lo;
+          HIPCHK(hipMemcpyAsync(dh, hent.data() + lo, 4 * cnt, hipMemcpyHostToDevice, c->stream));
+          d_hent = dh;
+          ++c->prime_parts;
+        }
+      }
+      CHK(verify_async_locked(c, cnt, d + 96 * lo, d + n * 96 + 32 * lo, staged_key(c, n, d, t, lo), dc + lo, d_hent));
     }
   }
   CHK(sync_all(c));
@@ -4314,6 +4531,8 @@ ovh_ctx* ovh_create(int device, const uint8_t* dst, size_t dst_len, uint32_t fla
   // same-message routing
   if (const char* e = getenv("OVH_SMALL_MAX")) c->small_max = (uint32_t)atoi(e);
   if (const char* e = getenv("OVH_SAMEMSG")) c->samemsg = atoi(e);
+  if (const char* e = getenv("OVH_PRIME_SIGN")) c->prime_sign = atoi(e) != 0;
+  if (const char* e = getenv("OVH_PRIME_BATCH")) c->prime_batch = atoi(e) != 0;
   if (const char* e = getenv("OVH_SHARD_SPAN")) c->shard_span = (uint32_t)atoi(e);
   if (const char* e = getenv("OVH_SHARD_STREAMS")) c->shard_streams = atoi(e) == 3 ? 3u : 2u;
   if (const char* e = getenv("OVH_NFIN")) c->nfin = atoi(e) == 3 ? 3u : atoi(e) == 2 ? 2u : NFIN_STREAMS;
@@ -4469,8 +4688,11 @@ static void destroy_one(ovh_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (hipStream_t s : {c->fstream, c->fstream2, c->fstream3, c->fstream4, c->xstream, c->vstream[0], c->vstream[1], c->vstream[2], c->pool_st[0],
-                        c->pool_st[1], c->pool_st[2], c->hstream[1], c->hstream[2], c->hstream[3]})
+                        c->pool_st[1], c->pool_st[2], c->hstream[1], c->hstream[2], c->hstream[3], c->prime_st})
     if (s) (void)hipStreamSynchronize(s);
+  if (c->prime_slab) (void)hipFree(c->prime_slab);
+  for (hipEvent_t e : {c->prime_ev0, c->prime_ev})
+    if (e) (void)hipEventDestroy(e);
   for (int k = 0; k < OVH_BATCH_SLOTS; ++k)
     for (void* p : {(void*)c->grp_ok[k], (void*)c->msm_buf[k], (void*)c->gslab[k]})
       if (p) (void)hipFree(p);
@@ -4505,7 +4727,8 @@ static void destroy_one(ovh_ctx* c) {
   }
   // the streams are parked, not destroyed (stream_new)
   for (hipStream_t s : {c->stream, c->fstream, c->fstream2, c->fstream3, c->fstream4, c->xstream, c->vstream[0], c->vstream[1], c->vstream[2],
-                        c->pool_st[0], c->pool_st[1], c->pool_st[2], c->hstream[1], c->hstream[2], c->hstream[3]})
+                        c->pool_st[0], c->pool_st[1], c->pool_st[2], c->hstream[1], c->hstream[2], c->hstream[3],
+                        c->prime_st})
     stream_park(c->device, s);
   if (c->pool_err) (void)hipHostFree(c->pool_err);
   delete c;
@@ -4758,14 +4981,18 @@ static int upload_blinds(ovh_ctx* c, size_t n, uint32_t first, uint32_t planes, 
 
 // n signatures on c->stream: hash_to_field per hash (k_h2f, u planes in scr), then the VM
 // (k_vm_sign). Caller holds c->mu and has sized scr for n.
-static int enqueue_sign(ovh_ctx* c, size_t n, const uint8_t* d_sks, const uint8_t* d_hashes, uint8_t* d_sigs) {
+// he (ovh_sign on a hash in the message table): H of every signature from table entry *he
+// (signg0h), no hash_to_field.
+static int enqueue_sign(ovh_ctx* c, size_t n, const uint8_t* d_sks, const uint8_t* d_hashes, uint8_t* d_sigs,
+                        const uint32_t* he = nullptr) {
   Slab u{c->scr, c->scr_cap}, bl;
   static_assert(S_U + 4 <= 6, "u planes below the blinding planes");
   CHK(upload_blinds(c, n, 6, 2, &bl));
-  k_h2f<<<nblk(n), WG, 0, c->stream>>>((uint32_t)n, d_hashes, c->xmd, u);
+  if (!he) k_h2f<<<nblk(n), WG, 0, c->stream>>>((uint32_t)n, d_hashes, c->xmd, u);
   constexpr uint32_t SL = 64 / VM_SIGNG0_W;
-  k_vm_signg<<<(uint32_t)((n + SL - 1) / SL), 64, LDS_SIGNG, c->stream>>>((uint32_t)n, c->vm_signg0, c->vm_signg1,
-                                                                          c->vm_consts, d_sks, u, d_sigs, bl);
+  k_vm_signg<<<(uint32_t)((n + SL - 1) / SL), 64, LDS_SIGNG, c->stream>>>(
+      (uint32_t)n, he ? c->vm_signg0h : c->vm_signg0, c->vm_signg1, c->vm_consts, d_sks, u, d_sigs, bl,
+      he ? Slab{c->hc_planes, HC_CAP} : Slab{nullptr, 0}, he ? *he : 0u);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -4782,7 +5009,15 @@ int ovh_sign(ovh_ctx* c, const uint8_t* key, size_t key_len, const uint8_t* hash
   CHK(ensure_scr(c, 1));
   HIPCHK(hipMemcpyAsync(c->in_buf, sk.b, 32, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(c->in_buf + 32, hash, 32, hipMemcpyHostToDevice, c->stream));
-  CHK(enqueue_sign(c, 1, c->in_buf, c->in_buf + 32, c->in_buf + 64));
+  // a hash in the message table (ovh_prime_hashes): signg0h on its H. The lookup is keyed by the
+  // public hash only; a hash not in the table is signed as ever and is not entered.
+  uint32_t he = 0;
+  const bool primed = c->prime_sign && c->hc_planes && hc_find(c, std::string((const char*)hash, 32), &he);
+  if (primed) {
+    CHK(hc_touch(c));
+    ++c->prime_signs;
+  }
+  CHK(enqueue_sign(c, 1, c->in_buf, c->in_buf + 32, c->in_buf + 64, primed ? &he : nullptr));
   // the scalar does not outlive the call: staging bytes zeroed after the kernel, host copy wiped
   HIPCHK(hipMemsetAsync(c->in_buf, 0, 32, c->stream));
   HIPCHK(hipMemcpyAsync(out, c->in_buf + 64, 96, hipMemcpyDeviceToHost, c->stream));
@@ -5366,6 +5601,29 @@ int ovh_msg_cache_stats(ovh_ctx* c, uint64_t stats[2]) {
     std::lock_guard<std::mutex> g(s->mu);
     stats[0] += s->hc_hits;
     stats[1] += s->hc_misses;
+  }
+  return 0;
+}
+
+int ovh_prime_hashes(ovh_ctx* c, size_t k, const uint8_t* hashes) {
+  if (!c || (k && !hashes) || k > OVH_PRIME_MAX) return OVH_ERR_ARG;
+  if (k == 0) return 0;
+  for (ovh_ctx* s : devices_of(c)) {
+    std::lock_guard<std::mutex> g(s->mu);
+    CHK(prime_locked(s, k, hashes));
+  }
+  return 0;
+}
+
+int ovh_prime_stats(ovh_ctx* c, uint64_t stats[4]) {
+  if (!c || !stats) return OVH_ERR_ARG;
+  stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  for (ovh_ctx* s : devices_of(c)) {
+    std::lock_guard<std::mutex> g(s->mu);
+    stats[0] += s->prime_enq;
+    stats[1] += s->prime_skip;
+    stats[2] += s->prime_signs;
+    stats[3] += s->prime_parts;
   }
   return 0;
 }

@@ -21,6 +21,12 @@ QC / one proposal per round); they first flush what is held, so overlord sees ev
 arrival order, as the reference's proc_network_msg forwards them. A message that does not
 decode is dropped with a warning, as the reference does.
 
+Priming: every vote of a group signs the same hash, so when a held vote or choke is the first
+with its signed hash since the last flush, the shim primes that hash at once
+(`ConsensusCrypto.prime` -> `ovh_prime_hashes`, which returns without waiting for the device):
+hash_to_G2 of the hash runs while the rest of the group arrives, and the flush's batch runs on
+the cached H.
+
 Wire layouts [dep: overlord 0.4 types + rlp 0.5, not vendored; named assumption 7 in DESIGN.md]:
   SignedVote   = rlp([signature bytes, Vote, voter bytes])
   Vote         = rlp([height u64, round u64, vote_type u8, block_hash bytes])  (vote.rlp_vote)
@@ -148,6 +154,7 @@ class VoteIngress:
         self.clock = clock
         self.pending: List[_Pending] = []
         self.groups: Dict[Tuple[int, int, int], int] = {}
+        self.primed: set = set()    # signed hashes primed since the last flush
         self.stats = {"batches": 0, "prefetched": 0, "forwarded": 0, "dropped": 0, "unbatched": 0}
 
     def _limit(self) -> int:
@@ -184,6 +191,12 @@ class VoteIngress:
 
     def _hold(self, kind, m, key, sig, voter) -> None:
         self.pending.append(_Pending(kind, m, sig, voter, self.clock()))
+        if hasattr(self.crypto, "prime"):
+            # the first message with this signed hash since the last flush: H(m) ahead of the batch
+            h = self.crypto.hash(m.vote_rlp() if kind == SIGNED_VOTE else m.hash_rlp())
+            if len(h) == 32 and h not in self.primed:
+                self.primed.add(h)
+                self.crypto.prime([h])
         self.groups[key] = self.groups.get(key, 0) + 1
         if self.groups[key] >= self._limit():
             self.flush()
@@ -209,6 +222,7 @@ class VoteIngress:
     def flush(self) -> None:
         """Batch-verify every held message (one prefetch), then forward them in arrival order."""
         items, self.pending, self.groups = self.pending, [], {}
+        self.primed = set()
         if not items:
             return
         hs = self._hashes(items)

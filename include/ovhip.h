@@ -194,6 +194,28 @@ int ovh_samemsg_stats(ovh_ctx* ctx, uint64_t stats[3]);
  * votes of a round sign the same hash, consensus.rs:397-416) skips hash_to_G2. stats[0] = hits,
  * stats[1] = misses, summed over a multi-device context's devices. */
 int ovh_msg_cache_stats(ovh_ctx* ctx, uint64_t stats[2]);
+/* Prime the message cache ahead of a round: the bytes a node signs or verifies are known before
+ * the signature is made or arrives (hash(rlp(Vote{height, round, type, block_hash})) carries no
+ * voter: at proposal receipt the block's prevote and precommit hashes, at round start the nil
+ * votes and the choke). Enqueues hash_to_G2 of every one of the k hashes (k x 32 bytes, k <=
+ * OVH_PRIME_MAX) that is not in the 256-entry message cache, on a side stream of the context,
+ * and returns without waiting for the device; hashes already cached or repeated in the call cost
+ * no device work. Work that reads or fills the cache afterwards waits for the prime on the
+ * device; work that does not touch the cache never waits for it. Consumers of a primed hash:
+ * the per-call verify (a cache hit on the first vote), ovh_sign (the signature bytes are those of
+ * an unprimed sign; a hash not in the cache is signed as before and is not entered), and
+ * ovh_verify_batch / ovh_prefetch on one device for a part (the table-key votes or the other
+ * votes of a call) of 2 .. OVH_SMALL_MAX votes outside the same-message route whose hashes are
+ * all in the cache. The environment variables OVH_PRIME_SIGN and OVH_PRIME_BATCH (read at
+ * ovh_create, 1 / 0) turn the sign and batch consumers on or off (defaults: DESIGN.md section
+ * 3.6). A multi-device context primes every device. Returns OVH_ERR_ARG for a NULL context, NULL
+ * hashes with k > 0 or k > OVH_PRIME_MAX (nothing is enqueued), 0 for k = 0. */
+#define OVH_PRIME_MAX 64
+int ovh_prime_hashes(ovh_ctx* ctx, size_t k, const uint8_t* hashes /* k x 32 */);
+/* stats[0] = hashes for which device work was enqueued, stats[1] = hashes skipped (cached or
+ * repeated), stats[2] = ovh_sign calls served from the cache, stats[3] = small-batch parts run on
+ * cached H; since ovh_create, summed over a multi-device context's devices. */
+int ovh_prime_stats(ovh_ctx* ctx, uint64_t stats[4]);
 
 /* Batched QC verification for block sync (check_block, consensus.rs:143-207): QC j = aggregated
  * signature sigs[j] (96 B) over hashes[j] (32 B, the SM3 of rlp(Vote{h, r, Precommit, block})),

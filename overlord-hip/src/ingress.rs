@@ -23,7 +23,7 @@ use crate::{ffi, HipCrypto};
 use bytes::Bytes;
 use overlord::types::{AggregatedVote, OverlordMsg, SignedChoke, SignedProposal, SignedVote};
 use overlord::Codec;
-use std::collections::HashMap;
+use std::collections::{HashMap, HashSet};
 use std::time::{Duration, Instant};
 
 /// Group key kind of a choke (vote kinds are Prevote 0 / Precommit 1).
@@ -57,6 +57,8 @@ pub struct VoteIngress<T: Codec, F: FnMut(OverlordMsg<T>)> {
     forward: F,
     held: Vec<Held<T>>,
     groups: HashMap<(u64, u64, u8), usize>,
+    /// signed hashes primed since the last flush (`HipCrypto::prime_hashes`)
+    primed: HashSet<[u8; 32]>,
     /// None: the validator count (minus one for a validator), from `HipCrypto::pubkeys`
     pub batch_size: Option<usize>,
     pub max_delay: Duration,
@@ -70,6 +72,7 @@ impl<T: Codec, F: FnMut(OverlordMsg<T>)> VoteIngress<T, F> {
             forward,
             held: Vec::new(),
             groups: HashMap::new(),
+            primed: HashSet::new(),
             batch_size: None,
             max_delay: Duration::from_millis(2),
             stats: IngressStats::default(),
@@ -136,6 +139,19 @@ impl<T: Codec, F: FnMut(OverlordMsg<T>)> VoteIngress<T, F> {
 
     async fn hold(&mut self, msg: OverlordMsg<T>, key: (u64, u64, u8), sig: Bytes, voter: Bytes,
                   vote: Option<(u64, u64, u8, Bytes)>, choke: Option<(u64, u64)>) {
+        // the first message with this signed hash since the last flush: prime H(m) at once, so
+        // hash_to_G2 runs while the rest of the group arrives and the flush's batch takes the
+        // primed route. ovh_prime_hashes does not wait for the device, but it takes the context
+        // mutex, which a blocking call may hold: a blocking task, not awaited
+        let h = host_hash(&self.crypto, &(vote.clone(), choke));
+        if let Ok(h32) = <[u8; 32]>::try_from(&h[..]) {
+            if self.primed.insert(h32) {
+                let crypto = self.crypto.clone();
+                tokio::task::spawn_blocking(move || {
+                    let _ = crypto.prime_hashes(&[h32]);
+                });
+            }
+        }
         self.held.push(Held { msg, sig, voter, vote, choke, t: Instant::now() });
         let c = self.groups.entry(key).or_insert(0);
         *c += 1;
@@ -157,6 +173,7 @@ impl<T: Codec, F: FnMut(OverlordMsg<T>)> VoteIngress<T, F> {
     pub async fn flush(&mut self) {
         let items = std::mem::take(&mut self.held);
         self.groups.clear();
+        self.primed.clear();
         if items.is_empty() {
             return;
         }
@@ -204,7 +221,6 @@ impl<T: Codec, F: FnMut(OverlordMsg<T>)> VoteIngress<T, F> {
 /// The signed hash of every held message: device vote digests for votes whose block hash
 /// fits OVH_VOTE_HASH_MAX, Crypto::hash (SM3) of the RLP otherwise and for chokes.
 fn signed_hashes(crypto: &HipCrypto, items: &[(Option<(u64, u64, u8, Bytes)>, Option<(u64, u64)>)]) -> Vec<Bytes> {
-    use overlord::Crypto;
     let mut out: Vec<Option<Bytes>> = vec![None; items.len()];
     let idx: Vec<usize> = (0..items.len())
         .filter(|&i| matches!(&items[i].0, Some((_, _, _, bh)) if bh.len() <= ffi::OVH_VOTE_HASH_MAX))
@@ -222,26 +238,31 @@ fn signed_hashes(crypto: &HipCrypto, items: &[(Option<(u64, u64, u8, Bytes)>, Op
         }
     }
     for (i, it) in items.iter().enumerate() {
-        if out[i].is_some() {
-            continue;
+        if out[i].is_none() {
+            out[i] = Some(host_hash(crypto, it));
         }
-        let mut s = rlp::RlpStream::new();
-        match it {
-            (Some((h, r, t, bh)), _) => {
-                s.begin_list(4);
-                s.append(h);
-                s.append(r);
-                s.append(t);
-                s.append(&bh.to_vec());
-            }
-            (None, Some((h, r))) => {
-                s.begin_list(2);
-                s.append(h);
-                s.append(r);
-            }
-            _ => unreachable!(),
-        }
-        out[i] = Some(crypto.hash(Bytes::from(s.out().to_vec())));
     }
     out.into_iter().map(|h| h.unwrap()).collect()
+}
+
+/// Crypto::hash (SM3 on the host) of the RLP a vote or a choke signs.
+fn host_hash(crypto: &HipCrypto, it: &(Option<(u64, u64, u8, Bytes)>, Option<(u64, u64)>)) -> Bytes {
+    use overlord::Crypto;
+    let mut s = rlp::RlpStream::new();
+    match it {
+        (Some((h, r, t, bh)), _) => {
+            s.begin_list(4);
+            s.append(h);
+            s.append(r);
+            s.append(t);
+            s.append(&bh.to_vec());
+        }
+        (None, Some((h, r))) => {
+            s.begin_list(2);
+            s.append(h);
+            s.append(r);
+        }
+        _ => unreachable!(),
+    }
+    crypto.hash(Bytes::from(s.out().to_vec()))
 }

@@ -208,6 +208,26 @@ impl HipCrypto {
         })
     }
 
+    /// Prime H(m) of hashes this node is about to sign or verify (`ovh_prime_hashes`): enqueues
+    /// hash_to_G2 of every hash not yet in the context's message cache on a side stream and
+    /// returns without waiting for the device. Call it at proposal receipt (the block's prevote
+    /// and precommit hashes), at round start (the nil votes and the choke) and from the ingress
+    /// shim on the first vote of a group. Chunks by `OVH_PRIME_MAX`.
+    pub fn prime_hashes(&self, hashes: &[[u8; 32]]) -> Result<(), Box<dyn Error + Send>> {
+        for chunk in hashes.chunks(ffi::OVH_PRIME_MAX) {
+            check(unsafe { ffi::ovh_prime_hashes(self.raw(), chunk.len(), chunk.as_ptr() as *const u8) })?;
+        }
+        Ok(())
+    }
+
+    /// `ovh_prime_stats`: [hashes enqueued, hashes skipped (cached or repeated), signs served
+    /// from the cache, small-batch parts run on cached H].
+    pub fn prime_stats(&self) -> Result<[u64; 4], Box<dyn Error + Send>> {
+        let mut st = [0u64; 4];
+        check(unsafe { ffi::ovh_prime_stats(self.raw(), st.as_mut_ptr()) })?;
+        Ok(st)
+    }
+
     /// hash(rlp(Vote)) of n votes on the device (`ovh_vote_digests`: rlp + SM3 per vote, the
     /// bytes overlord signs, consensus.rs:169-175). `block_hashes` holds one hash per vote of at
     /// most OVH_VOTE_HASH_MAX bytes. Blocking.

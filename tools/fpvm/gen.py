@@ -30,7 +30,7 @@ KZERO, KTAB = 1, 2   # fixed constant-table entries (fpvm.hpp)
 WIDTH = {"vote": 16, "vote_t": 16, "fold": 64, "final": 64, "rs": 16, "madd": 8, "padd": 8}
 WIDTH.update({"hdbl%d" % m: 16 for m in progs.HDBL_M})
 WIDTH.update({"votew": 64, "votew_t": 64, "qcpre": 64, "qcmil": 64, "vote1h": 64, "vote_t1h": 64, "pkgen": 16,
-              "signg0": 32, "signg1": 32})   # sign: per call a 32-lane slice (r03y: 2,280 -> 2,123 phases, -14% est.)
+              "signg0": 32, "signg1": 32, "signg0h": 32, "votewh": 64, "votewh_t": 64})   # sign: per call a 32-lane slice (r03y: 2,280 -> 2,123 phases, -14% est.)
 WIDTH.update({"sigchk": 16, "pkchk": 16, "g1padd": 8, "vote1": 64, "vote_t1": 64,
               "final1": 64})
 # same-message batches (r04): per vote a 16-lane slice, per distinct hash one 16-lane slice for
@@ -38,12 +38,16 @@ WIDTH.update({"sigchk": 16, "pkchk": 16, "g1padd": 8, "vote1": 64, "vote_t1": 64
 WIDTH.update({"vsame": 16, "vsame_t": 16, "h2g": 16, "gmil": 64, "pkdec": 4, "g1grp": 16, "gfin": 64})
 WIDTH.update({"vsame8": 8, "vsame8_t": 8})   # large same-message batches: eight votes per wave
 MAX_SLOTS = {"gfin": 2048, "vsame": 400, "vsame_t": 400, "vsame8": 400, "vsame8_t": 400, "h2g": 400, "gmil": 1200, "vote": 200, "vote_t": 200, "fold": 256, "final": 2048, "final1": 2048, "vote1": 1200, "vote_t1": 1200,
-             "votew": 1200, "votew_t": 1200, "qcpre": 1200, "qcmil": 1200, "vote1h": 1200, "vote_t1h": 1200}
+             "votew": 1200, "votew_t": 1200, "votewh": 1200, "votewh_t": 1200, "qcpre": 1200, "qcmil": 1200, "vote1h": 1200, "vote_t1h": 1200}
 # phases an op may run ahead of its first consumer's earliest start (sched.schedule `hoist`)
 HOIST = {"gfin": 50, "vsame": 250, "vsame_t": 250, "vsame8": 250, "vsame8_t": 250, "h2g": 250, "gmil": 250, "vote": 250, "vote_t": 250, "final": 50, "vote1": 250, "vote_t1": 250, "final1": 50, "votew": 250,
-         "votew_t": 250, "qcpre": 250, "qcmil": 250, "vote1h": 250, "vote_t1h": 250}
+         "votew_t": 250, "qcpre": 250, "qcmil": 250, "vote1h": 250, "vote_t1h": 250,
+         # H is an input: the key side and the signature side are live at once. Hoist 250 needs 854 /
+         # 813 slots (three workgroups per CU, so a 1,024-vote batch would run in two rounds); hoist 10
+         # needs 779 / 737 at the same 2,081 phases and cost estimate: four per CU, one round
+         "votewh": 10, "votewh_t": 10}
 STRETCH = {"gfin": 1.0, "vsame": 1.0, "vsame_t": 1.0, "vsame8": 1.0, "vsame8_t": 1.0, "h2g": 1.0, "gmil": 1.0, "final": 1.0, "vote": 1.0, "vote_t": 1.0, "vote1": 1.0, "vote_t1": 1.0, "final1": 1.0, "votew": 1.0,
-           "votew_t": 1.0, "qcpre": 1.0, "qcmil": 1.0, "vote1h": 1.0, "vote_t1h": 1.0}
+           "votew_t": 1.0, "qcpre": 1.0, "qcmil": 1.0, "vote1h": 1.0, "vote_t1h": 1.0, "votewh": 1.0, "votewh_t": 1.0}
 # priority weight of a heavy op against a light one (path length in weighted ops). r03 scan on
 # the cost model (product phase 1.60 us, linear 0.69 us): vote 4 -> 64 estimates 3.29 -> 3.10 ms
 # (a product on the path outweighs any run of light ops); vote_t keeps 2
@@ -72,7 +76,7 @@ SEC_BIAS = {"vote_t": {"sig": 1500}}
 # sign 3.08 -> 3.00, QC 4.41 -> 4.33, config 5 5.8 -> 5.6 ms. The batch final keeps mixing (its
 # slots would outgrow the LDS budget).
 NOMIX = set(filter(None, os.environ.get(
-    "OVH_GEN_NOMIX", "vote,vote_t,vote1,vote_t1,vote1h,vote_t1h,final1,qcpre,qcmil,votew,votew_t,signg0,signg1,"
+    "OVH_GEN_NOMIX", "vote,vote_t,vote1,vote_t1,vote1h,vote_t1h,final1,qcpre,qcmil,votew,votew_t,votewh,votewh_t,signg0,signg0h,signg1,"
     "sigchk,pkchk,pkgen,vsame,vsame_t,vsame8,vsame8_t,h2g,gmil,pkdec,g1grp").split(",")))
 # r04: the batch vote programs keep at most SPILL_K values in LDS per phase; the rest wait in the
 # vote's global scratch (sched.spill_pass: side-word spills / fills beside the lane ops), so a
@@ -285,8 +289,10 @@ def check(built):
     check_votew(built, bls, g)
     check_qc_split(built, bls, g)
     check_vote1h(built, bls, g)
+    check_votewh(built, bls, g)
     check_pkgen(built, bls, g)
     check_signg(built, bls, g)
+    check_signg0h(built, bls, g)
     check_samemsg(built, bls, g)
     print("fpvm check: vote/vote_t/rs/fold/final/MSM/sigchk/pkchk/g1padd programs match the oracle and their DAGs")
 
@@ -499,6 +505,68 @@ def check_vote1h(built, bls, g):
             assert sched.simulate(tsc, tw, tin, 1) == tref, "vote_t1h: simulated"
         for FF in (F, [tref["st:f%d" % k] for k in range(12)]):
             assert fprog.evaluate(dict(zip(fins, FF)))[fprog.outputs["ok"]] == want, "vote1h + final1"
+
+
+def check_votewh(built, bls, g):
+    """Small batches on primed hashes: vote1's stored H fed to votewh / votewh_t gives exactly
+    votew's / votew_t's twelve f values for the same r, on a golden vote and on one with another
+    vote's signature, on the DAG and in the slot-level simulator; FE(f) == 1 iff the vote
+    verifies."""
+    v1 = built["vote1"][0]
+    wp, tp = built["votew"][0], built["votew_t"][0]
+    hp, hsc, hw, hins, _ = built["votewh"]
+    htp, htsc, htw, htins, _ = built["votewh_t"]
+    fprog, _, _, fins, _ = built["final1"]
+    vs, ks = g["votes"][:2], g["keys"][:2]
+    for sig_from, want, r in ((0, 1, 0x9E3779B97F4A7C15), (1, 0, 0x1234567890ABCDEF)):
+        pkb, h = bytes.fromhex(ks[0]["pk"]), bytes.fromhex(vs[0]["digest"])
+        inp = vote_inputs(bls, pkb, bytes.fromhex(vs[sig_from]["sig"]), h)
+        v = v1.evaluate(inp, 1)
+        H = {"h%d" % k: v[v1.outputs["st:h%d" % k]] for k in range(6)}
+        wv = wp.evaluate(inp, r)
+        F = [wv[wp.outputs["st:f%d" % k]] for k in range(12)]
+        hin = {k: inp[k] for k in ("pk_x", "pk_sort", "sig_x0", "sig_x1", "sig_sort")}
+        hin.update(H)
+        assert set(hin) == set(hins)
+        hv = hp.evaluate(hin, r)
+        href = {n: hv[i] for n, i in hp.outputs.items()}
+        assert [href["st:f%d" % k] for k in range(12)] == F, "votewh == votew"
+        assert sched.simulate(hsc, hw, hin, r) == href, "votewh: simulated"
+        assert [href[n] for n in progs.VOTE1H_OUT] == [wv[wp.outputs[n]] for n in progs.VOTE1H_OUT], "votewh: flags"
+        pk = bls.g1_from_bytes(pkb)
+        tin = {k: inp[k] for k in ("sig_x0", "sig_x1", "sig_sort", "u00", "u01", "u10", "u11")}
+        tin.update(pk_X=pk[0] * 7 % P, pk_Y=pk[1] * 7 % P, pk_Z=7)
+        tv = tp.evaluate(tin, r)
+        TF = [tv[tp.outputs["st:f%d" % k]] for k in range(12)]
+        htin = {k: tin[k] for k in ("sig_x0", "sig_x1", "sig_sort", "pk_X", "pk_Y", "pk_Z")}
+        htin.update(H)
+        assert set(htin) == set(htins)
+        htv = htp.evaluate(htin, r)
+        htref = {n: htv[i] for n, i in htp.outputs.items()}
+        assert [htref["st:f%d" % k] for k in range(12)] == TF, "votewh_t == votew_t"
+        assert sched.simulate(htsc, htw, htin, r) == htref, "votewh_t: simulated"
+        for FF in (F, TF):
+            assert fprog.evaluate(dict(zip(fins, FF)))[fprog.outputs["ok"]] == want, "votewh + final1"
+
+
+def check_signg0h(built, bls, g):
+    """Sign on a primed hash: vote1's stored H fed to signg0h gives exactly signg0's 96 outputs
+    for the same launch scalar, on the DAG and in the slot-level simulator."""
+    v1 = built["vote1"][0]
+    p0 = built["signg0"][0]
+    ph, sh, wh, hins, houts = built["signg0h"]
+    for k, v in list(zip(g["keys"], g["votes"]))[:2]:
+        inp = vote_inputs(bls, bytes.fromhex(k["pk"]), bytes.fromhex(v["sig"]), bytes.fromhex(v["digest"]))
+        vv = v1.evaluate(inp, 1)
+        hin = {"h%d" % j: vv[v1.outputs["st:h%d" % j]] for j in range(6)}
+        assert set(hin) == set(hins)
+        sc = signg_scalar(gls_digits(int(k["sk"], 16)), 0)
+        want = p0.evaluate({n: inp[n] for n in progs.SIGN0_IN}, sc)
+        want = {n: want[i] for n, i in p0.outputs.items()}
+        got = ph.evaluate(hin, sc)
+        got = {n: got[i] for n, i in ph.outputs.items()}
+        assert len(houts) == 96 and got == want, "signg0h == signg0"
+        assert sched.simulate(sh, wh, hin, sc) == got, "signg0h: simulated"
 
 
 def check_pkgen(built, bls, g):

@@ -262,6 +262,41 @@ def build_votew(table: bool):
     return build
 
 
+def build_votewh(table: bool):
+    """votewh / votewh_t: votew / votew_t with H = hash_to_G2(hash) from the message table (a
+    small batch on primed hashes, ovhip.hip k_vm_votewh): inputs and flag outputs as vote1h /
+    vote_t1h, the same f for the same RLC scalar. Without hash_to_G2 the key side (r pk and its
+    Miller loop) and the signature side are live at once, so the slot file is larger than
+    votew's although the program is shorter."""
+    def build():
+        p = Prog("votewh_t" if table else "votewh")
+        a = Alg(p, use_sop=USE_SOP, fast_sqrt=True)
+        R = p.const(R_MONT)
+        if table:
+            Pp = (p.input("pk_X"), p.input("pk_Y"), p.input("pk_Z"))
+        else:
+            pk_ok, (px, py) = a.g1_decompress(p.input("pk_x") * R, p.input("pk_sort"))
+            Pp = (px, py, p.one)
+            pk_grp, _ = a.g1_in_group(Pp)
+        sx = (p.input("sig_x0") * R, p.input("sig_x1") * R)
+        H = unflat_g2p([p.input(n) for n in g2p_names("h")])
+        p.section = "sig"
+        sig_ok, (qx, qy) = a.g2_decompress(sx, p.input("sig_sort"))
+        Qs = (qx, qy, (p.one, p.zero))
+        sig_grp = a.g2_in_group(Qs)
+        rS = a.pt_mul_glv("f2", Qs, a.g2_neg_psi2(Qs))
+        p.section = None
+        rP = a.pt_mul_glv("fp", Pp, a.g1_phi(Pp))
+        f = a.f12_mul(a.miller_loop_multi([(rP, H)]), a.miller_loop_multi([((p.const(G1X), p.const(-G1Y)), rS)]))
+        flags = [sig_ok, sig_grp] if table else [pk_ok, pk_grp, sig_ok, sig_grp]
+        for name, v in zip(VOTE_T1H_OUT if table else VOTE1H_OUT, flags):
+            p.output(name, v)
+        for (name, plane), v in zip(VOTE1_ST, flat12(f)):
+            p.store(name, v, plane)
+        return p
+    return build
+
+
 QCPRE_IN = ["sig_x0", "sig_x1", "sig_sort", "u00", "u01", "u10", "u11"]
 QCPRE_OUT = ["sig_ok", "sig_grp", "h_inf"]
 QCPRE_ST = [(n, S_RS + k) for k, n in enumerate(g2p_names("h"))] + [(n, S_F + k) for k, n in enumerate(f12_names("g"))]
@@ -520,6 +555,24 @@ def build_signg0():
     return p
 
 
+SIGNG0H_IN = g2p_names("h")
+
+
+def build_signg0h():
+    """signg0 with H = hash_to_G2(hash) from the message table (ovh_sign on a primed hash): the
+    table of sums and the first 16 chain steps only; the same 96 outputs, so signg1 follows
+    unchanged."""
+    p = Prog("signg0h")
+    a = Alg(p, use_sop=USE_SOP)
+    H = unflat_g2p([p.input(n) for n in SIGNG0H_IN])
+    T = _gls_table(a, H)
+    acc = _signg_steps(a, None, T, first=True)
+    flat_t = [c for pt in T for c in flat_g2p(pt)]
+    for name, v in zip(SIGN_ACC + SIGNG_T, flat_g2p(acc) + flat_t):
+        p.output(name, v)
+    return p
+
+
 def build_signg1():
     """The next 16 GLS chain steps (run three times)."""
     p = Prog("signg1")
@@ -626,6 +679,9 @@ PROGRAMS["qcmil"] = (build_qcmil, QCMIL_IN, [])
 PROGRAMS["votew"] = (build_votew(False), VOTE_IN, VOTE_OUT)
 PROGRAMS["votew_t"] = (build_votew(True), VOTE_T_IN, VOTE_T_OUT)
 PROGRAMS["g1padd"] = (build_g1padd, G1A_IN + G1B_IN, G1_OUT)
+PROGRAMS["votewh"] = (build_votewh(False), VOTE1H_IN, VOTE1H_OUT)
+PROGRAMS["votewh_t"] = (build_votewh(True), VOTE_T1H_IN, VOTE_T1H_OUT)
+PROGRAMS["signg0h"] = (build_signg0h, SIGNG0H_IN, SIGN_ACC + SIGNG_T)
 
 # ---------------------------------------------------------------- same-message batches (r04)
 # Every vote of a round signs the same hash (consensus.rs:169-175: Vote has no voter field), so
