@@ -6023,6 +6023,47 @@ static int ensure_qcg(ovh_ctx* c, size_t words) {
   return 0;
 }
 
+// Batch state for a QC pass over n votes: ensure_cap, with room in the slot's MSM tree slab
+// (msm_acap(cap) entries) for the padded segments' tree of ovh_build_qcs (32 entries per chunk,
+// <= n / 2 + 32 G; sg empty for ovh_build_qc). qc_seg_cap: the capacity that tree needs -- 64
+// singleton groups need 2,048 entries against 2,044 at cap 256.
+static size_t qc_seg_cap(const QcSegments& sg) { return sg.entries > MSM_NB ? (sg.entries - MSM_NB + 3) / 4 : 0; }
+static int ensure_qc_cap(ovh_ctx* c, size_t n, const QcSegments& sg) {
+  const size_t ecap = qc_seg_cap(sg);
+  CHK(ensure_cap(c, ecap > n ? ecap : n));
+  if (msm_acap(c->cap) < sg.entries) return OVH_ERR_ARG;
+  return 0;
+}
+
+// The selection (qc.hpp) over n staged votes, the first t of them of table voters (a table of tn
+// entries) -> owner, bitmap, count and taken of `sel`.
+static void enqueue_qc_select(hipStream_t st, uint32_t tn, uint32_t n, uint32_t t, const QcSel& sel) {
+  k_qc_reset<<<nblk((size_t)sel.groups * tn), WG, 0, st>>>(tn, sel);
+  if (t) k_qc_claim<<<nblk(t), WG, 0, st>>>(tn, t, sel);
+  k_qc_mark<<<nblk(n), WG, 0, st>>>(tn, n, t, sel);
+}
+
+// The masked G2 sum (qc.hpp) of the taken sigma of n >= 2 votes in a.st, and its compression.
+// sg null: one sum over all votes -> a.A[0] -> 96 bytes at out96. Else one sum per group of the
+// segment layout sg (dlist, dseg: its list and segment table on the device) -> a.A[32 seg[2 g]]
+// -> 96 bytes per group.
+static void enqueue_qc_sum(ovh_ctx* c, hipStream_t st, const MsmArgs& a, uint32_t n, const uint32_t* dtaken,
+                           const QcSegments* sg, const uint32_t* dlist, const uint32_t* dseg, uint8_t* out96) {
+  if (sg) {
+    const uint32_t G = (uint32_t)(sg->seg.size() / 2);
+    k_qc_chunk<true><<<sg->chunks, 64, LDS_MSM8, st>>>(n, dtaken, dlist, c->vm_madd, c->vm_padd, MSM8_STRIDE_W,
+                                                      c->vm_consts, a);
+    if (sg->chunks > G)  // a group of more than one chunk
+      k_qc_upper<true><<<G, 64, LDS_MSM8, st>>>(0, dseg, c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
+    k_qc_compress<<<G, 64, 0, st>>>(a.A, dseg, out96);
+  } else {
+    k_qc_chunk<false><<<(n + MSM_CH - 1) >> MSM_CH_LV, 64, LDS_MSM8, st>>>(n, dtaken, nullptr, c->vm_madd, c->vm_padd,
+                                                                          MSM8_STRIDE_W, c->vm_consts, a);
+    if (n > MSM_CH) k_qc_upper<false><<<1, 64, LDS_MSM8, st>>>(n, nullptr, c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
+    k_g2p_compress<<<1, 64, 0, st>>>(a.A, out96);
+  }
+}
+
 // ovh_build_qc on one device (caller holds c->mu, the table is set): the round's verify batch on
 // the same-message path (every vote signs `hash`; its vote program leaves each sigma, affine and
 // subgroup-checked, in the slot's state slab), then on the batch's final stream, behind the
@@ -6061,11 +6102,7 @@ static int build_qc_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint
   const size_t qoff = (pl.off + pl.bytes + lbytes + 255) / 256 * 256;
   const size_t zoff = qoff + 8 * n, ooff = zoff + 16;
   CHK(ensure_in(c, ooff + 96 * (size_t)G));
-  // the padded segments' tree (32 entries per chunk, <= n / 2 + 32 G) has to fit the slot's MSM
-  // tree slab, msm_acap(cap) entries: 64 singleton groups need 2,048 against 2,044 at cap 256
-  const size_t ecap = sg.entries > MSM_NB ? (sg.entries - MSM_NB + 3) / 4 : 0;
-  CHK(ensure_cap(c, ecap > n ? ecap : n));
-  if (msm_acap(c->cap) < sg.entries) return OVH_ERR_ARG;
+  CHK(ensure_qc_cap(c, n, sg));
   if (mo) CHK(ensure_qcg(c, (size_t)G * ((size_t)tb.n + bw + 1)));
   uint8_t* d = c->in_buf;
   int32_t* dc = (int32_t*)(d + n * 176);
@@ -6148,28 +6185,17 @@ static int build_qc_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint
     sel.count = sel.bitmap + tb.cap / 32;
   }
   sel.taken = dtaken;
-  k_qc_reset<<<nblk((size_t)G * tb.n), WG, 0, st>>>(tb.n, sel);
-  if (t) k_qc_claim<<<nblk(t), WG, 0, st>>>(tb.n, (uint32_t)t, sel);
-  k_qc_mark<<<nblk(n), WG, 0, st>>>(tb.n, N, (uint32_t)t, sel);
+  enqueue_qc_select(st, tb.n, N, (uint32_t)t, sel);
   if (mo) {
     const uint32_t* dlist = (const uint32_t*)(d + pl.off + pl.bytes);
-    const uint32_t* dseg = dlist + sg.list.size();
-    k_qc_chunk<true><<<sg.chunks, 64, LDS_MSM8, st>>>(N, dtaken, dlist, c->vm_madd, c->vm_padd, MSM8_STRIDE_W,
-                                                     c->vm_consts, a);
-    if (sg.chunks > G)  // a group of more than one chunk
-      k_qc_upper<true><<<G, 64, LDS_MSM8, st>>>(0, dseg, c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
-    k_qc_compress<<<G, 64, 0, st>>>(a.A, dseg, d + ooff);
-  } else {
-    if (n == 1) {
-      constexpr uint32_t SL = 64 / VM_SIGCHK_W;
-      k_vm_sigchk<<<(1 + SL - 1) / SL, 64, LDS_SIGCHK, st>>>(1, c->vm_sigchk, c->vm_consts, d, (const uint64_t*)(d + zoff),
-                                                             0, (int32_t*)(d + zoff + 8), a.A);
-    } else {
-      k_qc_chunk<false><<<(N + MSM_CH - 1) >> MSM_CH_LV, 64, LDS_MSM8, st>>>(N, dtaken, nullptr, c->vm_madd, c->vm_padd,
-                                                                            MSM8_STRIDE_W, c->vm_consts, a);
-      if (N > MSM_CH) k_qc_upper<false><<<1, 64, LDS_MSM8, st>>>(N, nullptr, c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
-    }
+    enqueue_qc_sum(c, st, a, N, dtaken, &sg, dlist, dlist + sg.list.size(), d + ooff);
+  } else if (n == 1) {
+    constexpr uint32_t SL = 64 / VM_SIGCHK_W;
+    k_vm_sigchk<<<(1 + SL - 1) / SL, 64, LDS_SIGCHK, st>>>(1, c->vm_sigchk, c->vm_consts, d, (const uint64_t*)(d + zoff), 0,
+                                                           (int32_t*)(d + zoff + 8), a.A);
     k_g2p_compress<<<1, 64, 0, st>>>(a.A, d + ooff);
+  } else {
+    enqueue_qc_sum(c, st, a, N, dtaken, nullptr, nullptr, nullptr, d + ooff);
   }
   HIPCHK(hipGetLastError());
   drain.s[1] = st;

@@ -11,13 +11,17 @@ invalid-then-valid and a non-member at those sizes.
 
     sigma + G2 (code 5), the golden sig_not_in_g2 (3), the golden pk_x_eq_p (102), a validly
     signed vote from a key outside the table, an exact duplicate of a valid vote, a voter whose
-    first vote is sigma + G2 and whose second is valid."""
+    first vote is sigma + G2 and whose second is valid.
+
+The last three tests are rounds of related keys (a validator beside its mirror, a validator that
+is a combination of three others): their sums double and cancel, which unrelated keys never do."""
 import ctypes
 import random
 
 import numpy as np
 import pytest
 
+import bls12_381 as bls
 import orc
 import qc_model
 import synth_votes as sv
@@ -82,7 +86,8 @@ def _verify_code(cc, sig, digest, voter):
         return 102
 
 
-def _check_round(cc, sigs, voters, table, digest, cache=True):
+def _check_round(cc, sigs, voters, table, digest, cache=True, qc_code=0):
+    """qc_code: what verifying the built QC must give (None: whatever the oracle gives)"""
     from consensus_overlord_amd import vote
     n = len(sigs)
     cc.update_pubkeys(table)
@@ -98,8 +103,9 @@ def _check_round(cc, sigs, voters, table, digest, cache=True):
         ts = [s for s, t in zip(sigs, m_taken) if t]
         tv = [p for p, t in zip(voters, m_taken) if t]
         assert (0, agg) == orc.aggregate_sigs(ts, tv)
-        assert orc.verify_aggregated(agg, digest, vote.extract_voters(table, bitmap)) == 0
-        assert cc.verify_qc_batch([agg], [digest], [bitmap]).tolist() == [0]
+        want_qc = orc.verify_aggregated(agg, digest, vote.extract_voters(table, bitmap))
+        assert qc_code is None or want_qc == qc_code
+        assert cc.verify_qc_batch([agg], [digest], [bitmap]).tolist() == [want_qc]
         assert agg == cc.aggregate_signatures(ts, tv)          # the two-call path agrees
         got = cc.build_qc(sigs, digest, voters)
         assert got[0] == agg and got[1] == bitmap
@@ -206,3 +212,69 @@ def test_multi_device_context(cc, golden):
     digest = sv.sha(b"build_qc multi")
     sigs, voters, table = _make_round(cc.ctx, golden, 97600, 70, digest)
     _check_round(mc, sigs, voters, table, digest)
+
+
+# ------------------------------------------------------------------------------ related keys
+# Votes whose keys and signatures are related, made from device-signed votes without any secret:
+# the sums of a round's sigma (and of a QC's keys) then double or cancel, which unrelated keys
+# never do. Where they meet in the device's trees depends on the staging; the exact-placement
+# claims are tests/test_gpu_qc_kernels.py's.
+def _mirror(sig, pk):
+    """(-sigma, -pk): the valid vote of the validator with secret r - sk (the sign bit of both
+    compressed encodings flipped)"""
+    return bytes([sig[0] ^ 0x20]) + sig[1:], bytes([pk[0] ^ 0x20]) + pk[1:]
+
+
+def _combination(a, b, c):
+    """(sigma_a + sigma_b - sigma_c, pk_a + pk_b - pk_c) of three (sig, pk): the valid vote of the
+    validator with secret sk_a + sk_b - sk_c, over the Python oracle"""
+    F2, F1 = bls.Fp2Ops, bls.FpOps
+    s = [bls.g2_from_bytes(x[0]) for x in (a, b, c)]
+    k = [bls.g1_from_bytes(x[1]) for x in (a, b, c)]
+    sig = bls.pt_add(F2, bls.pt_add(F2, s[0], s[1]), bls.pt_neg(F2, s[2]))
+    pk = bls.pt_add(F1, bls.pt_add(F1, k[0], k[1]), bls.pt_neg(F1, k[2]))
+    return bls.g2_compress(sig), bls.g1_compress(pk)
+
+
+def _votes(ctx, lo, n, digest):
+    sg, pk = _round(ctx, lo, n, digest)
+    return [(bytes(s), bytes(p)) for s, p in zip(sg, pk)]
+
+
+def _check_related(cc, votes, digest):
+    sigs, voters = [v[0] for v in votes], [v[1] for v in votes]
+    assert len(set(voters)) == len(voters)
+    want, taken, _, agg = _check_round(cc, sigs, voters, voters, digest, qc_code=None)
+    assert not want.any() and all(taken)
+    return agg
+
+
+def test_round_of_a_validator_and_its_mirror(cc):
+    """sigma + (-sigma): the aggregate is the compressed identity, the aggregated key is infinite"""
+    digest = sv.sha(b"build_qc mirror")
+    v = _votes(cc.ctx, 98000, 1, digest)[0]
+    m = _mirror(*v)
+    assert orc.verify(m[0], digest, m[1]) == 0
+    assert _check_related(cc, [v, m], digest) == bls.g2_compress(None)
+    assert _check_related(cc, [m, v], digest) == bls.g2_compress(None)
+
+
+def test_round_with_a_combination_validator(cc):
+    """votes a, b, c, d = a + b - c at positions 0 to 3 of a round of 8: sigma_a + sigma_b equals
+    sigma_c + sigma_d"""
+    digest = sv.sha(b"build_qc combination")
+    v = _votes(cc.ctx, 98100, 7, digest)
+    d = _combination(v[0], v[1], v[2])
+    assert orc.verify(d[0], digest, d[1]) == 0
+    agg = _check_related(cc, v[:3] + [d] + v[3:], digest)
+    assert agg != bls.g2_compress(None)
+
+
+def test_round_whose_second_chunk_mirrors_its_first(cc):
+    """130 votes: votes 64 .. 127 are the mirrors of votes 0 .. 63, two more follow; the aggregate
+    is the sum of the last two"""
+    digest = sv.sha(b"build_qc mirrored chunk")
+    v = _votes(cc.ctx, 98200, 66, digest)
+    votes = v[:64] + [_mirror(*x) for x in v[:64]] + v[64:]
+    agg = _check_related(cc, votes, digest)
+    assert (0, agg) == orc.aggregate_sigs([x[0] for x in v[64:]], [x[1] for x in v[64:]])
