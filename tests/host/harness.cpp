@@ -121,6 +121,83 @@ int hx_g1_subgroup(const uint8_t* in, uint32_t len) {
   return g1_in_subgroup(j) ? 1 : 0;
 }
 
+// The decoders' exact point (tests/point_cases.py): the code of g*_from_bytes, and the affine
+// coordinates as 48-byte BE canonical values (G1: x, y; G2: x.c1, x.c0, y.c1, y.c0) whenever the
+// decoder set the point: code 0 (not infinity), and code 3 for x = 0.
+int hx_g1_decode_xy(const uint8_t* in, uint32_t len, uint8_t* out96, int* inf) {
+  G1A a;
+  bool i;
+  int e = g1_from_bytes(a, i, in, len);
+  *inf = i;
+  if ((e == 0 && !i) || e == BLST_POINT_NOT_IN_GROUP) {
+    fp_to_be48(out96, a.x);
+    fp_to_be48(out96 + 48, a.y);
+  }
+  return e;
+}
+
+int hx_g2_decode_xy(const uint8_t* in, uint32_t len, uint8_t* out192, int* inf) {
+  G2A a;
+  bool i;
+  int e = g2_from_bytes(a, i, in, len);
+  *inf = i;
+  if ((e == 0 && !i) || e == BLST_POINT_NOT_IN_GROUP) {
+    fp_to_be48(out192, a.x.c1);
+    fp_to_be48(out192 + 48, a.x.c0);
+    fp_to_be48(out192 + 96, a.y.c1);
+    fp_to_be48(out192 + 144, a.y.c0);
+  }
+  return e;
+}
+
+// The subgroup checks on an affine point given by its coordinates (layout as above), past the
+// decoder: the order-3 points (0, +-2) reach the ladders this way. -1: a coordinate >= p.
+int hx_g1_subgroup_xy(const uint8_t* xy96) {
+  G1A a;
+  if (!fp_from_be48_masked(a.x, xy96, false) || !fp_from_be48_masked(a.y, xy96 + 48, false)) return -1;
+  G1J j; jac_from_aff(j, a);
+  return g1_in_subgroup(j) ? 1 : 0;
+}
+
+int hx_g2_subgroup_xy(const uint8_t* xy192) {
+  G2A a;
+  if (!fp_from_be48_masked(a.x.c1, xy192, false) || !fp_from_be48_masked(a.x.c0, xy192 + 48, false) ||
+      !fp_from_be48_masked(a.y.c1, xy192 + 96, false) || !fp_from_be48_masked(a.y.c0, xy192 + 144, false))
+    return -1;
+  G2J j; jac_from_aff(j, a);
+  return g2_in_subgroup(j) ? 1 : 0;
+}
+
+// [|x|] P by jac_mul_xabs, the ladder of both subgroup checks, on an affine point (layout as
+// above): 0 and the affine result, 1 for the identity, -1 for a coordinate >= p.
+int hx_g1_mul_xabs_xy(const uint8_t* xy96, uint8_t* out96) {
+  G1A a;
+  if (!fp_from_be48_masked(a.x, xy96, false) || !fp_from_be48_masked(a.y, xy96 + 48, false)) return -1;
+  G1J j, r;
+  jac_from_aff(j, a);
+  jac_mul_xabs(r, j);
+  if (!jac_to_aff(a, r)) return 1;
+  fp_to_be48(out96, a.x);
+  fp_to_be48(out96 + 48, a.y);
+  return 0;
+}
+
+int hx_g2_mul_xabs_xy(const uint8_t* xy192, uint8_t* out192) {
+  G2A a;
+  if (!fp_from_be48_masked(a.x.c1, xy192, false) || !fp_from_be48_masked(a.x.c0, xy192 + 48, false) ||
+      !fp_from_be48_masked(a.y.c1, xy192 + 96, false) || !fp_from_be48_masked(a.y.c0, xy192 + 144, false))
+    return -1;
+  G2J j, r;
+  jac_from_aff(j, a);
+  jac_mul_xabs(r, j);
+  if (!jac_to_aff(a, r)) return 1;
+  fp_to_be48(out192, a.x.c1);
+  fp_to_be48(out192 + 48, a.x.c0);
+  fp_to_be48(out192 + 96, a.y.c1);
+  fp_to_be48(out192 + 144, a.y.c0);
+  return 0;
+}
+
 // The VM's modular inverse (fpvm.hpp fp_inv) on a raw canonical value: r3 = raw R turns the
 // closing Montgomery product into the identity, so out = a^-1 mod p (0 -> 0).
 void hx_fp_inv_raw(const uint32_t* a, const uint32_t* r_raw, uint32_t* out) {
