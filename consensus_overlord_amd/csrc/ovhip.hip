@@ -304,6 +304,26 @@ __device__ __forceinline__ void slot_put(uint32_t* slots, uint32_t s, const uint
 
 __device__ __forceinline__ uint32_t slot_flag_get(const uint32_t* slots, uint32_t s) { return slots[s * 12]; }
 
+// Slot s as a canonical Fp: slots hold [0, 2p) representatives (fpvm.hpp); HBM planes are canonical.
+__device__ __forceinline__ void slot_get_canon(const uint32_t* slots, uint32_t s, Fp& v) {
+  for (int l = 0; l < 12; ++l) v.v[l] = slots[s * 12 + l];
+  vm::canon(v, v);
+}
+
+// A VM kernel's dynamic LDS: the constant table, loaded here, and the slots of the unit that
+// starts `off` words into the slot area. The kernels that still spell this out (rs, g1pairs, gmil,
+// gfin, g2tree, pkgen, signg, g1tree, the MSM's) or the slot read above (g2tree, g1tree,
+// msm_pair_op) compile to other code with the helper; they stay until a change may move it.
+struct VmLds {
+  uint32_t *cst, *slots;
+};
+__device__ __forceinline__ VmLds vm_lds(const uint32_t* __restrict__ cst_g, uint32_t off = 0) {
+  extern __shared__ uint4 lds4[];
+  uint32_t* lds = reinterpret_cast<uint32_t*>(lds4);
+  load_consts(lds, cst_g, VM_NCONST);
+  return {lds, lds + SLOT_BASE_W + off};
+}
+
 // One fold unit on a 16-lane slice: out[t] = (prod F, sum S) over in[4t .. 4t+3] (missing ->
 // identity); with codes (level 0) every vote whose code is not 0 contributes the identity.
 // inS.p null: every S is the identity (the batch path's S is the MSM's, msm.hpp).
@@ -334,9 +354,7 @@ __device__ __forceinline__ void fold_unit(uint32_t t, uint32_t m, const VmDev& p
   if (active) {
     for (uint32_t k = lane; k < PART_PLANES; k += VM_FOLD_W) {
       Fp v;
-      const uint32_t src = VM_FOLD_OUT[k];
-      for (int q = 0; q < 12; ++q) v.v[q] = slots[src * 12 + q];
-      vm::canon(v, v);  // slots hold [0, 2p) representatives (fpvm.hpp); planes are canonical
+      slot_get_canon(slots, VM_FOLD_OUT[k], v);
       out.st(v, k, t);
     }
   }
@@ -943,15 +961,11 @@ __global__ __launch_bounds__(64) void k_vm_fold(uint32_t m, VmDev prog, const ui
                                                 const int32_t* __restrict__ gate = nullptr) {
   if (gate && *gate == 1) return;
   __builtin_amdgcn_s_setprio(2);  // short, as the pool's waves
-  extern __shared__ uint4 lds4[];
-  uint32_t* lds = reinterpret_cast<uint32_t*>(lds4);
-  uint32_t* cst = lds;
   const uint32_t slice = threadIdx.x / VM_FOLD_W, lane = threadIdx.x % VM_FOLD_W;
   const uint32_t sl = slice < SLICES ? slice : 0;  // idle slices address slice 0 (never write)
-  uint32_t* slots = lds + SLOT_BASE_W + sl * FOLD_STRIDE_W;
+  auto [cst, slots] = vm_lds(cst_g, sl * FOLD_STRIDE_W);
   const uint32_t t = blockIdx.x * SLICES + slice;
   const bool active = slice < SLICES && 4 * t < m;
-  load_consts(cst, cst_g, VM_NCONST);
   fold_unit(t, m, prog, cst, slots, lane, active, inF, inS, out, codes);
 }
 
@@ -963,12 +977,8 @@ __global__ __launch_bounds__(64) void k_vm_final(uint32_t m, VmDev prog, const u
   // 4.2 ms instead of 2.1 at equal or lower priority; its slot ran out first (r05p trace). With
   // this and the MSM levels at 2: 1,432k verifs/s vs 1,131k-1,316k (r05q A/B)
   __builtin_amdgcn_s_setprio(3);
-  extern __shared__ uint4 lds4[];
-  uint32_t* lds = reinterpret_cast<uint32_t*>(lds4);
-  uint32_t* cst = lds;
-  uint32_t* slots = lds + SLOT_BASE_W;
+  auto [cst, slots] = vm_lds(cst_g);
   const uint32_t lane = threadIdx.x;
-  load_consts(cst, cst_g, VM_NCONST);
   for (uint32_t k = lane; k < 4 * PART_PLANES; k += 64) {
     const uint32_t q = k / PART_PLANES, j = k % PART_PLANES;
     Fp v;
@@ -1020,13 +1030,9 @@ __device__ __forceinline__ void vote_wave(const VmDev& prog, uint32_t nph, uint3
                                           int32_t* __restrict__ code, Slab hc = Slab{nullptr, 0}, uint32_t he = 0,
                                           const uint32_t* __restrict__ hinf_in = nullptr,
                                           uint32_t* __restrict__ hinf_out = nullptr) {
-  extern __shared__ uint4 lds4[];
-  uint32_t* lds = reinterpret_cast<uint32_t*>(lds4);
-  uint32_t* cst = lds;
-  uint32_t* slots = lds + SLOT_BASE_W;
+  auto [cst, slots] = vm_lds(cst_g);
   uint32_t* hdr = slots + ns * 12;  // [sig flags, pk flags]
   const uint32_t lane = threadIdx.x;
-  load_consts(cst, cst_g, VM_NCONST);
   if (lane == 0) {
     uint32_t x1[12], x0[12], bad, inf, sort, xz;
     parse_hdr(sig, 96, x1, x0, bad, inf, sort, xz);
@@ -1254,14 +1260,11 @@ __global__ __launch_bounds__(64) void k_vm_vsame(uint32_t cnt, uint32_t lo, VmDe
                                                  const uint32_t* __restrict__ cst_g, const uint8_t* __restrict__ pks,
                                                  PkSrc pk, const uint8_t* __restrict__ sigs, Slab s, uint64_t seed,
                                                  uint64_t base, int32_t* __restrict__ codes) {
-  extern __shared__ uint4 lds4[];
   if (SM_PRIO) __builtin_amdgcn_s_setprio(2);
-  uint32_t* lds = reinterpret_cast<uint32_t*>(lds4);
-  uint32_t* cst = lds;
   static_assert(W == 16 || W == 8, "vsame slice width");
   constexpr bool W8 = W == 8;
   const uint32_t slice = threadIdx.x / W, lane = threadIdx.x % W;
-  uint32_t* slots = lds + SLOT_BASE_W + slice * (W8 ? VSAME8_STRIDE_W : VSAME_STRIDE_W);
+  auto [cst, slots] = vm_lds(cst_g, slice * (W8 ? VSAME8_STRIDE_W : VSAME_STRIDE_W));
   constexpr uint32_t NS = W8 ? (TABLE ? VM_VSAME8_T_NSLOTS : VM_VSAME8_NSLOTS)
                              : (TABLE ? VM_VSAME_T_NSLOTS : VM_VSAME_NSLOTS);
   uint32_t* hdr = slots + NS * 12;  // [sig flags, key flags]
@@ -1269,7 +1272,6 @@ __global__ __launch_bounds__(64) void k_vm_vsame(uint32_t cnt, uint32_t lo, VmDe
   const uint16_t* OUT = W8 ? (TABLE ? VM_VSAME8_T_OUT : VM_VSAME8_OUT) : (TABLE ? VM_VSAME_T_OUT : VM_VSAME_OUT);
   const uint32_t j = blockIdx.x * (64 / W) + slice, i = lo + j;
   const bool active = j < cnt;
-  load_consts(cst, cst_g, VM_NCONST);
   if (active) {
     if (lane == 0) {
       uint32_t x1[12], x0[12], bad, inf, sort, xz;
@@ -1331,15 +1333,11 @@ __global__ __launch_bounds__(64) void k_vm_vsame(uint32_t cnt, uint32_t lo, VmDe
 // of group g, ghinf[g] = H is the identity.
 __global__ __launch_bounds__(64) void k_vm_h2g(uint32_t G, VmDev prog, const uint32_t* __restrict__ cst_g, Slab g,
                                                uint32_t* __restrict__ ghinf) {
-  extern __shared__ uint4 lds4[];
   if (SM_PRIO) __builtin_amdgcn_s_setprio(3);
-  uint32_t* lds = reinterpret_cast<uint32_t*>(lds4);
-  uint32_t* cst = lds;
   const uint32_t slice = threadIdx.x / 16, lane = threadIdx.x % 16;
-  uint32_t* slots = lds + SLOT_BASE_W + slice * H2G_STRIDE_W;
+  auto [cst, slots] = vm_lds(cst_g, slice * H2G_STRIDE_W);
   const uint32_t q = blockIdx.x * VM_SLICES + slice;
   const bool active = q < G;
-  load_consts(cst, cst_g, VM_NCONST);
   if (active && lane < 4) {
     Fp u;
     g.ld(u, VM_G_U + lane, q);
@@ -1399,9 +1397,7 @@ __global__ __launch_bounds__(64) void k_vm_g1pairs(uint32_t npairs, VmDev prog, 
   if (active) {
     for (uint32_t k = lane; k < 3; k += W) {
       Fp v;
-      const uint32_t src = prog.out[k];
-      for (int l = 0; l < 12; ++l) v.v[l] = slots[src * 12 + l];
-      vm::canon(v, v);
+      slot_get_canon(slots, prog.out[k], v);
       P.st(v, k, a);
     }
   }
@@ -1553,13 +1549,9 @@ __global__ __launch_bounds__(64) void k_vm_gfin(VmDev prog, const uint32_t* __re
 // | h_inf << 10.
 __global__ __launch_bounds__(64) void k_vm_qcpre(VmDev prog, const uint32_t* __restrict__ cst_g,
                                                  const uint8_t* __restrict__ sig, Slab s, uint32_t* __restrict__ flags) {
-  extern __shared__ uint4 lds4[];
-  uint32_t* lds = reinterpret_cast<uint32_t*>(lds4);
-  uint32_t* cst = lds;
-  uint32_t* slots = lds + SLOT_BASE_W;
+  auto [cst, slots] = vm_lds(cst_g);
   uint32_t* hdr = slots + VM_QCPRE_NSLOTS * 12;
   const uint32_t lane = threadIdx.x;
-  load_consts(cst, cst_g, VM_NCONST);
   if (lane == 0) {
     uint32_t x1[12], x0[12], bad, inf, sort, xz;
     parse_hdr(sig, 96, x1, x0, bad, inf, sort, xz);
@@ -1586,12 +1578,8 @@ __global__ __launch_bounds__(64) void k_vm_qcpre(VmDev prog, const uint32_t* __r
 // code in vote_t1's precedence (consensus.rs:397-416 via verify_aggregated_signature).
 __global__ __launch_bounds__(64) void k_vm_qcmil(VmDev prog, const uint32_t* __restrict__ cst_g, PkSrc pk, Slab s,
                                                  const uint32_t* __restrict__ flags, int32_t* __restrict__ code) {
-  extern __shared__ uint4 lds4[];
-  uint32_t* lds = reinterpret_cast<uint32_t*>(lds4);
-  uint32_t* cst = lds;
-  uint32_t* slots = lds + SLOT_BASE_W;
+  auto [cst, slots] = vm_lds(cst_g);
   const uint32_t lane = threadIdx.x;
-  load_consts(cst, cst_g, VM_NCONST);
   if (lane < 21) {
     Fp v;
     if (lane < 3) Slab{const_cast<uint32_t*>(pk.planes), pk.cap}.ld(v, lane, 0);
@@ -1622,12 +1610,8 @@ static_assert(VM_QCMIL_NIN == 21 && VM_QCPRE_W == 64 && VM_QCMIL_W == 64, "qcmil
 
 // FE(F_u) == 1 for unit u of the F planes (program final1): the shared body of the FE kernels.
 __device__ __forceinline__ bool fe_one(const VmDev& prog, const uint32_t* __restrict__ cst_g, Slab F, uint32_t u) {
-  extern __shared__ uint4 lds4[];
-  uint32_t* lds = reinterpret_cast<uint32_t*>(lds4);
-  uint32_t* cst = lds;
-  uint32_t* slots = lds + SLOT_BASE_W;
+  auto [cst, slots] = vm_lds(cst_g);
   const uint32_t lane = threadIdx.x;
-  load_consts(cst, cst_g, VM_NCONST);
   if (lane < 12) {
     Fp v;
     F.ld(v, lane, u);
@@ -1677,12 +1661,8 @@ __global__ __launch_bounds__(64) void k_vm_final1(VmDev prog, const uint32_t* __
 // partials are the identity): prod F * Miller(-G1, S) -> FE == 1.
 __device__ __forceinline__ bool final_one(uint32_t u, const VmDev& prog, const uint32_t* __restrict__ cst_g, Slab inF,
                                           Slab inS) {
-  extern __shared__ uint4 lds4[];
-  uint32_t* lds = reinterpret_cast<uint32_t*>(lds4);
-  uint32_t* cst = lds;
-  uint32_t* slots = lds + SLOT_BASE_W;
+  auto [cst, slots] = vm_lds(cst_g);
   const uint32_t lane = threadIdx.x;
-  load_consts(cst, cst_g, VM_NCONST);
   for (uint32_t k = lane; k < 4 * PART_PLANES; k += 64) {
     const uint32_t q = k / PART_PLANES, j = k % PART_PLANES;
     Fp v;
@@ -1764,15 +1744,11 @@ constexpr uint32_t SIGCHK_STRIDE_W = align256w(VM_SIGCHK_NSLOTS * 12 + 4);
 __global__ __launch_bounds__(64) void k_vm_sigchk(uint32_t n, VmDev prog, const uint32_t* __restrict__ cst_g,
                                                   const uint8_t* __restrict__ data, const uint64_t* __restrict__ off,
                                                   int gc, int32_t* __restrict__ codes, Slab pts) {
-  extern __shared__ uint4 lds4[];
-  uint32_t* lds = reinterpret_cast<uint32_t*>(lds4);
-  uint32_t* cst = lds;
   const uint32_t slice = threadIdx.x / VM_SIGCHK_W, lane = threadIdx.x % VM_SIGCHK_W;
-  uint32_t* slots = lds + SLOT_BASE_W + slice * SIGCHK_STRIDE_W;
+  auto [cst, slots] = vm_lds(cst_g, slice * SIGCHK_STRIDE_W);
   uint32_t* hdr = slots + VM_SIGCHK_NSLOTS * 12;
   const uint32_t i = blockIdx.x * (64 / VM_SIGCHK_W) + slice;
   const bool active = i < n;
-  load_consts(cst, cst_g, VM_NCONST);
   if (active && lane == 0) {
     uint32_t x1[12], x0[12], bad, inf, sort, xz;
     parse_hdr(data + off[i], 96, x1, x0, bad, inf, sort, xz);
@@ -1799,9 +1775,7 @@ __global__ __launch_bounds__(64) void k_vm_sigchk(uint32_t n, VmDev prog, const 
   for (uint32_t k = lane; k < 6; k += VM_SIGCHK_W) {
     Fp v;
     if (pt && k < 4) {
-      const uint32_t src = VM_SIGCHK_OUT[VM_SIGCHK_OUT_Q0 + k];
-      for (int l = 0; l < 12; ++l) v.v[l] = slots[src * 12 + l];
-      vm::canon(v, v);
+      slot_get_canon(slots, VM_SIGCHK_OUT[VM_SIGCHK_OUT_Q0 + k], v);
     } else if (k == (pt ? 4u : 2u)) {
       fp_one(v);
     } else {
@@ -1903,8 +1877,7 @@ __global__ __launch_bounds__(64) void k_vm_pkgen(uint32_t n, VmDev prog, const u
     __syncthreads();
     if (active && lane < 3) {
       Fp t;
-      for (int l = 0; l < 12; ++l) t.v[l] = slots[VM_PKGEN_OUT[lane] * 12 + l];
-      vm::canon(t, t);
+      slot_get_canon(slots, VM_PKGEN_OUT[lane], t);
       for (int l = 0; l < 12; ++l) acc[lane * 12 + l] = t.v[l];
     }
     __syncthreads();
@@ -2102,15 +2075,11 @@ __global__ __launch_bounds__(64) void k_vm_signg(uint32_t n, VmDev p0, VmDev p1,
 constexpr uint32_t PKCHK_STRIDE_W = align256w(VM_PKCHK_NSLOTS * 12 + 4);
 __global__ __launch_bounds__(64) void k_vm_pkchk(uint32_t n, VmDev prog, const uint32_t* __restrict__ cst_g,
                                                  const uint8_t* __restrict__ pks, Slab pts, uint32_t* __restrict__ flags) {
-  extern __shared__ uint4 lds4[];
-  uint32_t* lds = reinterpret_cast<uint32_t*>(lds4);
-  uint32_t* cst = lds;
   const uint32_t slice = threadIdx.x / VM_PKCHK_W, lane = threadIdx.x % VM_PKCHK_W;
-  uint32_t* slots = lds + SLOT_BASE_W + slice * PKCHK_STRIDE_W;
+  auto [cst, slots] = vm_lds(cst_g, slice * PKCHK_STRIDE_W);
   uint32_t* hdr = slots + VM_PKCHK_NSLOTS * 12;
   const uint32_t i = blockIdx.x * (64 / VM_PKCHK_W) + slice;
   const bool active = i < n;
-  load_consts(cst, cst_g, VM_NCONST);
   if (active && lane == 0) {
     uint32_t x[12], bad, inf, sort, xz;
     parse_hdr(pks + (size_t)i * 48, 48, x, x, bad, inf, sort, xz);
@@ -2132,9 +2101,7 @@ __global__ __launch_bounds__(64) void k_vm_pkchk(uint32_t n, VmDev prog, const u
   for (uint32_t k = lane; k < 3; k += VM_PKCHK_W) {
     Fp v;
     if (pt && k < 2) {
-      const uint32_t src = VM_PKCHK_OUT[VM_PKCHK_OUT_P0 + k];
-      for (int l = 0; l < 12; ++l) v.v[l] = slots[src * 12 + l];
-      vm::canon(v, v);
+      slot_get_canon(slots, VM_PKCHK_OUT[VM_PKCHK_OUT_P0 + k], v);
     } else if (k == (pt ? 2u : 1u)) {
       fp_one(v);
     } else {
@@ -2202,13 +2169,9 @@ __global__ __launch_bounds__(64) void k_apk_finish(Slab in, Slab out, uint32_t* 
 constexpr uint32_t G1GRP_STRIDE_W = align256w(VM_G1GRP_NSLOTS * 12);
 __global__ __launch_bounds__(64) void k_vm_g1grp(VmDev prog, const uint32_t* __restrict__ cst_g, Slab apk,
                                                  uint32_t* __restrict__ flags) {
-  extern __shared__ uint4 lds4[];
-  uint32_t* lds = reinterpret_cast<uint32_t*>(lds4);
-  uint32_t* cst = lds;
   const uint32_t slice = threadIdx.x / VM_G1GRP_W, lane = threadIdx.x % VM_G1GRP_W;
-  uint32_t* slots = lds + SLOT_BASE_W;
+  auto [cst, slots] = vm_lds(cst_g);
   const bool active = slice == 0;
-  load_consts(cst, cst_g, VM_NCONST);
   if (active && lane < 3) {
     Fp v;
     apk.ld(v, lane, 0);
@@ -2414,15 +2377,11 @@ __global__ __launch_bounds__(64) void k_vm_pkdec(uint32_t n, VmDev prog, const u
                                                  const uint8_t* __restrict__ data, const uint64_t* __restrict__ off,
                                                  int32_t* __restrict__ codes) {
   constexpr uint32_t W = VM_PKDEC_W, SL = 64 / W;
-  extern __shared__ uint4 lds4[];
-  uint32_t* lds = reinterpret_cast<uint32_t*>(lds4);
-  uint32_t* cst = lds;
   const uint32_t slice = threadIdx.x / W, lane = threadIdx.x % W;
-  uint32_t* slots = lds + SLOT_BASE_W + slice * PKDEC_STRIDE_W;
+  auto [cst, slots] = vm_lds(cst_g, slice * PKDEC_STRIDE_W);
   uint32_t* hdr = slots + VM_PKDEC_NSLOTS * 12;
   const uint32_t i = blockIdx.x * SL + slice;
   const bool active = i < n;
-  load_consts(cst, cst_g, VM_NCONST);
   if (active && lane == 0) {
     uint32_t x[12], bad, inf, sort, xz;
     parse_hdr(data + off[i], 48, x, x, bad, inf, sort, xz);
@@ -2546,8 +2505,7 @@ struct ovh_ctx {
   // on a final stream (lowest priority) while later batches' votes run. OVH_BATCH_SLOTS slots of
   // batch state rotate (a slot is reused only after its final-stream work finished). Batches
   // take the NFIN_STREAMS final streams in turn, so that many chains run at once.
-  hipStream_t fstream = nullptr, fstream2 = nullptr, fstream3 = nullptr;
-  hipStream_t fstream4 = nullptr;
+  hipStream_t fstream[NFIN_STREAMS] = {};  // [3] only with nfin = 4
   uint32_t nfin = NFIN_STREAMS;  // final streams in turn (OVH_NFIN: 2, 3 or 4, A/B)
   hipStream_t xstream = nullptr;  // per-call side work beside `stream` (aggregate_signatures' key parse; lazy)
   // ovh_verify_samemsg_device_async: [0], [1] the per-vote streams, in turn; [2] hash_to_G2 (lazy)
@@ -2636,10 +2594,16 @@ struct ovh_ctx {
   uint8_t* mg = nullptr;  // as a multi context's final device: OVH_BATCH_SLOTS x 16 gathered partials
   std::deque<HostBatch> hq;  // batches in flight (the root context / a single context)
   uint64_t hb_k = 0;
-  // Fp-VM programs + constant table in device memory
-  // same-message batches (verify_samemsg_locked): programs, per slot the group slab (G_PLANES
-  // planes + the H-is-infinity words, gcap entries); OVH_SAMEMSG=0 turns the path off
-  VmDev vm_vsame{}, vm_vsame_t{}, vm_vsame8{}, vm_vsame8_t{}, vm_h2g{}, vm_gmil{}, vm_pkdec{}, vm_g1grp{}, vm_gfin{};
+  // Fp-VM programs + constant table in device memory: one member per row of VM_TABLE below, in
+  // its order (vm_init uploads them)
+  VmDev vm_vote{}, vm_vote_t{}, vm_fold{}, vm_final{}, vm_rs{}, vm_sigchk{}, vm_pkchk{}, vm_vote1{}, vm_vote_t1{},
+      vm_signg0{}, vm_signg1{}, vm_pkgen{}, vm_vote1h{}, vm_vote_t1h{}, vm_qcpre{}, vm_qcmil{}, vm_votew{}, vm_votew_t{},
+      vm_votewh{}, vm_votewh_t{}, vm_signg0h{}, vm_final1{}, vm_vsame{}, vm_vsame_t{}, vm_vsame8{}, vm_vsame8_t{},
+      vm_h2g{}, vm_gfin{}, vm_g1grp{}, vm_pkdec{}, vm_gmil{}, vm_g1padd{}, vm_madd{}, vm_padd{}, vm_hdbl[5]{};
+  uint32_t* vm_consts = nullptr;
+  std::vector<void*> vm_bufs;
+  // same-message batches (verify_samemsg_locked): per slot the group slab (G_PLANES planes + the
+  // H-is-infinity words, gcap entries); OVH_SAMEMSG=0 turns the path off
   uint32_t* gslab[OVH_BATCH_SLOTS] = {};
   uint32_t gcap[OVH_BATCH_SLOTS] = {};
   // 0: off; 1 (default): batches above small_max votes (below it the small-batch path has the
@@ -2660,9 +2624,6 @@ struct ovh_ctx {
   size_t sm1_n = 0;
   std::vector<uint32_t> sm1_lo;
   uint8_t* sm1_hash = nullptr;
-  VmDev vm_vote{}, vm_vote_t{}, vm_fold{}, vm_final{}, vm_rs{}, vm_madd{}, vm_padd{}, vm_hdbl[5]{}, vm_sigchk{},
-      vm_pkchk{}, vm_g1padd{}, vm_vote1{}, vm_vote_t1{}, vm_final1{}, vm_votew{},
-      vm_votew_t{}, vm_qcpre{}, vm_qcmil{}, vm_vote1h{}, vm_vote_t1h{}, vm_pkgen{}, vm_signg0{}, vm_signg1{};
   // message cache (verify_one_locked): H = hash_to_G2(hash) of the last HC_CAP hashes verified
   // per call, projective planes + H-is-infinity flags, FIFO replacement
   uint32_t* hc_planes = nullptr;
@@ -2683,9 +2644,6 @@ struct ovh_ctx {
   // consumers of the cache beside the per-call verify (OVH_PRIME_SIGN / OVH_PRIME_BATCH, read
   // at ovh_create)
   bool prime_sign = true, prime_batch = true;
-  VmDev vm_votewh{}, vm_votewh_t{}, vm_signg0h{};
-  uint32_t* vm_consts = nullptr;
-  std::vector<void*> vm_bufs;
   uint32_t clk_wgs = 0;    // OVH_FLAG_VM_CLOCK: workgroups of the last vote launch
   bool clk_table = false;  // ... and whether it was vote_t
   std::vector<uint32_t> blind_h;  // host copy of the last compression blinds (upload_blinds)
@@ -2711,64 +2669,68 @@ struct ovh_ctx {
 
 static const char* const STAGE_NAMES[OVH_NSTAGES] = {"hash_to_field", "vote", "fold", "final", "bisect", "msm"};
 
-// LDS bytes of the VM kernels: constants + slices x slots (+ a 16-byte slice header for vote)
-static constexpr size_t LDS_VOTE = ((size_t)SLOT_BASE_W + VM_SLICES * (size_t)VOTE_STRIDE_W) * 4;
-static constexpr size_t LDS_VOTE_T = ((size_t)SLOT_BASE_W + VM_SLICES * (size_t)VOTE_T_STRIDE_W) * 4;
-static constexpr size_t LDS_FOLD = ((size_t)SLOT_BASE_W + VM_FOLD_UNITS * (size_t)FOLD_STRIDE_W) * 4;
-static constexpr size_t LDS_FINAL = ((size_t)SLOT_BASE_W + (size_t)VM_FINAL_NSLOTS * 12) * 4;
+// LDS bytes of the VM kernels: constants + units x the slot stride (the stride includes a slice's
+// 16-byte header where there is one) + extra words (the header of a one-unit kernel)
+constexpr size_t lds_bytes(uint32_t units, uint32_t stride_w, uint32_t extra_w = 0) {
+  return ((size_t)SLOT_BASE_W + (size_t)units * stride_w + extra_w) * 4;
+}
+static constexpr size_t LDS_VOTE = lds_bytes(VM_SLICES, VOTE_STRIDE_W);
+static constexpr size_t LDS_VOTE_T = lds_bytes(VM_SLICES, VOTE_T_STRIDE_W);
+static constexpr size_t LDS_FOLD = lds_bytes(VM_FOLD_UNITS, FOLD_STRIDE_W);
+static constexpr size_t LDS_FINAL = lds_bytes(1, VM_FINAL_NSLOTS * 12);
 static_assert(VM_VOTE_W * VM_SLICES == 64 && VM_VOTE_T_W * VM_SLICES == 64 && VM_FOLD_W * VM_FOLD_UNITS == 64 &&
                   VM_FINAL_W == 64, "VM slice widths");
-static constexpr size_t LDS_FOLD1 = ((size_t)SLOT_BASE_W + (size_t)FOLD_STRIDE_W) * 4;
+static constexpr size_t LDS_FOLD1 = lds_bytes(1, FOLD_STRIDE_W);
 // bisection r sigma and the MSM pair kernels (8-lane madd / padd, 16-lane hdbl<m>)
-static constexpr size_t LDS_RS = ((size_t)SLOT_BASE_W + (64 / VM_RS_W) * (size_t)RS_STRIDE_W) * 4;
+static constexpr size_t LDS_RS = lds_bytes(64 / VM_RS_W, RS_STRIDE_W);
 constexpr uint32_t cmax(uint32_t a, uint32_t b) { return a > b ? a : b; }
 static constexpr uint32_t MSM8_STRIDE_W = align128w(cmax(VM_MADD_NSLOTS, VM_PADD_NSLOTS) * 12);
 static constexpr uint32_t HDBL_STRIDE_W =
     align128w(cmax(cmax(cmax(VM_HDBL1_NSLOTS, VM_HDBL2_NSLOTS), cmax(VM_HDBL4_NSLOTS, VM_HDBL8_NSLOTS)), VM_HDBL16_NSLOTS) * 12);
-static constexpr size_t LDS_MSM8 = ((size_t)SLOT_BASE_W + (64 / VM_MADD_W) * (size_t)MSM8_STRIDE_W) * 4;
-static constexpr size_t LDS_HDBL = ((size_t)SLOT_BASE_W + (64 / VM_HDBL1_W) * (size_t)HDBL_STRIDE_W) * 4;
+static constexpr size_t LDS_MSM8 = lds_bytes(64 / VM_MADD_W, MSM8_STRIDE_W);
+static constexpr size_t LDS_HDBL = lds_bytes(64 / VM_HDBL1_W, HDBL_STRIDE_W);
 static_assert(VM_MADD_W == VM_PADD_W && VM_HDBL1_W == VM_HDBL2_W && VM_HDBL1_W == VM_HDBL4_W && VM_HDBL1_W == VM_HDBL8_W &&
                   VM_HDBL1_W == VM_HDBL16_W && VM_MADD_NIN == 10 && VM_PADD_NIN == 12 && VM_HDBL1_NIN == 12,
               "MSM program shapes (tools/fpvm/progs.py)");
-static constexpr size_t LDS_SIGCHK = ((size_t)SLOT_BASE_W + (64 / VM_SIGCHK_W) * (size_t)SIGCHK_STRIDE_W) * 4;
-static constexpr uint32_t VOTE1_NSLOTS = VM_VOTE1_NSLOTS > VM_VOTE_T1_NSLOTS ? VM_VOTE1_NSLOTS : VM_VOTE_T1_NSLOTS;
-static constexpr size_t LDS_VOTE1 = ((size_t)SLOT_BASE_W + VOTE1_NSLOTS * 12 + 4) * 4;
-static constexpr uint32_t VOTE1H_NSLOTS = VM_VOTE1H_NSLOTS > VM_VOTE_T1H_NSLOTS ? VM_VOTE1H_NSLOTS : VM_VOTE_T1H_NSLOTS;
-static constexpr size_t LDS_VOTE1H = ((size_t)SLOT_BASE_W + VOTE1H_NSLOTS * 12 + 4) * 4;
-static constexpr uint32_t VOTEW_NSLOTS = VM_VOTEW_NSLOTS > VM_VOTEW_T_NSLOTS ? VM_VOTEW_NSLOTS : VM_VOTEW_T_NSLOTS;
-static constexpr size_t LDS_VOTEW = ((size_t)SLOT_BASE_W + VOTEW_NSLOTS * 12 + 4) * 4;
+static constexpr size_t LDS_SIGCHK = lds_bytes(64 / VM_SIGCHK_W, SIGCHK_STRIDE_W);
+static constexpr uint32_t VOTE1_NSLOTS = cmax(VM_VOTE1_NSLOTS, VM_VOTE_T1_NSLOTS);
+static constexpr size_t LDS_VOTE1 = lds_bytes(1, VOTE1_NSLOTS * 12, 4);
+static constexpr uint32_t VOTE1H_NSLOTS = cmax(VM_VOTE1H_NSLOTS, VM_VOTE_T1H_NSLOTS);
+static constexpr size_t LDS_VOTE1H = lds_bytes(1, VOTE1H_NSLOTS * 12, 4);
+static constexpr uint32_t VOTEW_NSLOTS = cmax(VM_VOTEW_NSLOTS, VM_VOTEW_T_NSLOTS);
+static constexpr size_t LDS_VOTEW = lds_bytes(1, VOTEW_NSLOTS * 12, 4);
 // votewh / votewh_t hold the key side and the signature side at once (no hash_to_G2 to run the
 // signature's half beside): a larger slot file than votew's, so fewer workgroups per CU. A part
 // goes to k_vm_votewh only if its waves are co-resident (one round of the 256 CUs), as votew's
 // are for every small batch: VOTEWH_MAX votes.
-static constexpr uint32_t VOTEWH_NSLOTS = VM_VOTEWH_NSLOTS > VM_VOTEWH_T_NSLOTS ? VM_VOTEWH_NSLOTS : VM_VOTEWH_T_NSLOTS;
-static constexpr size_t LDS_VOTEWH = ((size_t)SLOT_BASE_W + VOTEWH_NSLOTS * 12 + 4) * 4;
-static constexpr size_t LDS_QCPRE = ((size_t)SLOT_BASE_W + VM_QCPRE_NSLOTS * 12 + 4) * 4;
-static constexpr size_t LDS_QCMIL = ((size_t)SLOT_BASE_W + VM_QCMIL_NSLOTS * 12) * 4;
-static constexpr size_t LDS_FINAL1 = ((size_t)SLOT_BASE_W + (size_t)VM_FINAL1_NSLOTS * 12) * 4;
-static constexpr size_t LDS_SIGNG = ((size_t)SLOT_BASE_W + (64 / VM_SIGNG0_W) * (size_t)SIGNG_STRIDE_W) * 4;
+static constexpr uint32_t VOTEWH_NSLOTS = cmax(VM_VOTEWH_NSLOTS, VM_VOTEWH_T_NSLOTS);
+static constexpr size_t LDS_VOTEWH = lds_bytes(1, VOTEWH_NSLOTS * 12, 4);
+static constexpr size_t LDS_QCPRE = lds_bytes(1, VM_QCPRE_NSLOTS * 12, 4);
+static constexpr size_t LDS_QCMIL = lds_bytes(1, VM_QCMIL_NSLOTS * 12);
+static constexpr size_t LDS_FINAL1 = lds_bytes(1, VM_FINAL1_NSLOTS * 12);
+static constexpr size_t LDS_SIGNG = lds_bytes(64 / VM_SIGNG0_W, SIGNG_STRIDE_W);
 static_assert(LDS_SIGNG <= 80 * 1024, "signg LDS (raised limit, ovh_create)");
-static constexpr size_t LDS_PKGEN = ((size_t)SLOT_BASE_W + (64 / VM_PKGEN_W) * (size_t)PKGEN_STRIDE_W) * 4;
-static constexpr size_t LDS_PKCHK = ((size_t)SLOT_BASE_W + (64 / VM_PKCHK_W) * (size_t)PKCHK_STRIDE_W) * 4;
+static constexpr size_t LDS_PKGEN = lds_bytes(64 / VM_PKGEN_W, PKGEN_STRIDE_W);
+static constexpr size_t LDS_PKCHK = lds_bytes(64 / VM_PKCHK_W, PKCHK_STRIDE_W);
 static constexpr uint32_t G1PADD_STRIDE_W = align128w(VM_G1PADD_NSLOTS * 12);
-static constexpr size_t LDS_G1PADD = ((size_t)SLOT_BASE_W + (64 / VM_G1PADD_W) * (size_t)G1PADD_STRIDE_W) * 4;
+static constexpr size_t LDS_G1PADD = lds_bytes(64 / VM_G1PADD_W, G1PADD_STRIDE_W);
 static_assert(LDS_RS <= 64 * 1024 && LDS_MSM8 <= 64 * 1024 && LDS_HDBL <= 64 * 1024 && LDS_SIGCHK <= 64 * 1024 &&
                   LDS_PKCHK <= 64 * 1024 && LDS_G1PADD <= 64 * 1024 && LDS_PKGEN <= 64 * 1024 &&
                   LDS_VOTE1 <= 64 * 1024 && LDS_FINAL1 <= 64 * 1024 && LDS_VOTEW <= 64 * 1024 && LDS_QCPRE <= 64 * 1024 && LDS_VOTE1H <= 64 * 1024 &&
                   LDS_QCMIL <= 64 * 1024 && VM_G1PADD_NIN == 6,
               "default LDS limit");
 static_assert(LDS_VOTE <= 160 * 1024 && LDS_VOTE_T <= 160 * 1024 && LDS_FINAL <= 160 * 1024, "VM LDS budget");
-static constexpr size_t LDS_VSAME = ((size_t)SLOT_BASE_W + VM_SLICES * (size_t)VSAME_STRIDE_W) * 4;
-static constexpr size_t LDS_VSAME8 = ((size_t)SLOT_BASE_W + 8 * (size_t)VSAME8_STRIDE_W) * 4;
+static constexpr size_t LDS_VSAME = lds_bytes(VM_SLICES, VSAME_STRIDE_W);
+static constexpr size_t LDS_VSAME8 = lds_bytes(8, VSAME8_STRIDE_W);
 static_assert(LDS_VSAME8 <= 64 * 1024, "vsame8 LDS (default limit)");
-static constexpr size_t LDS_H2G = ((size_t)SLOT_BASE_W + VM_SLICES * (size_t)H2G_STRIDE_W) * 4;
-static constexpr size_t LDS_GMIL = ((size_t)SLOT_BASE_W + (size_t)VM_GMIL_NSLOTS * 12) * 4;
+static constexpr size_t LDS_H2G = lds_bytes(VM_SLICES, H2G_STRIDE_W);
+static constexpr size_t LDS_GMIL = lds_bytes(1, VM_GMIL_NSLOTS * 12);
 static_assert(LDS_VSAME <= 64 * 1024 && LDS_H2G <= 64 * 1024 && LDS_GMIL + 16 <= 64 * 1024, "same-message LDS");
-static constexpr size_t LDS_PKDEC = ((size_t)SLOT_BASE_W + (64 / VM_PKDEC_W) * (size_t)PKDEC_STRIDE_W) * 4;
+static constexpr size_t LDS_PKDEC = lds_bytes(64 / VM_PKDEC_W, PKDEC_STRIDE_W);
 static_assert(LDS_PKDEC <= 64 * 1024 && VM_PKDEC_NIN == 2, "pkdec LDS / shape");
-static constexpr size_t LDS_G1GRP = ((size_t)SLOT_BASE_W + (size_t)G1GRP_STRIDE_W) * 4;
+static constexpr size_t LDS_G1GRP = lds_bytes(1, G1GRP_STRIDE_W);
 static_assert(LDS_G1GRP <= 64 * 1024 && VM_G1GRP_NIN == 3, "g1grp LDS / shape");
-static constexpr size_t LDS_GFIN = ((size_t)SLOT_BASE_W + (size_t)VM_GFIN_NSLOTS * 12) * 4;
+static constexpr size_t LDS_GFIN = lds_bytes(1, VM_GFIN_NSLOTS * 12);
 static_assert(LDS_GFIN + 16 <= 64 * 1024, "gfin LDS");
 // a CU holds its four vote workgroups beside the two finals that may be in flight (1 KiB
 // allocation granules assumed)
@@ -2796,38 +2758,107 @@ static_assert(VOTE_NSCR <= 4096 && VM_VOTE_NSLOTS <= 2048 && VM_VOTE_T_NSLOTS <=
 static_assert(FOLD_STRIDE_W <= VM_SLICES * VOTE_STRIDE_W && FOLD_STRIDE_W <= VM_SLICES * VOTE_T_STRIDE_W,
               "fused fold reuses the vote slots");
 
-static int vm_upload(ovh_ctx* c, VmDev& d, const uint32_t* code, uint32_t nphases, uint32_t W, uint32_t NW,
-                     const uint16_t* in, uint32_t nin, const uint16_t* out, uint32_t nout,
-                     const uint32_t* side = nullptr) {
+// A generated program on the host (vm_progs.inc): what vm_upload copies to the device. side:
+// the side words of a spilled program (VM_<PROG>_NSCR > 0: vote and vote_t unless
+// OVH_GEN_SPILL builds them without; the generator emits VM_<PROG>_SIDE only then), else null.
+struct VmProg {
+  const uint32_t* code;
+  uint32_t nphases, W, NW;
+  const uint16_t* in; uint32_t nin; const uint16_t* out; uint32_t nout;
+  const uint32_t* side;
+};
+#define VM_PROG(P, ...) \
+  VmProg { VM_##P##_CODE, VM_##P##_NPHASES, VM_##P##_W, VM_##P##_NW, VM_##P##_IN, VM_##P##_NIN, VM_##P##_OUT, VM_##P##_NOUT, __VA_ARGS__ }
+#if VM_VOTE_NSCR == 0
+#define VM_VOTE_SIDE nullptr
+#endif
+#if VM_VOTE_T_NSCR == 0
+#define VM_VOTE_T_SIDE nullptr
+#endif
+// Every program of the context: where its device copy lives in ovh_ctx and the generated
+// program. vm_init uploads them in this order. A new program is one member and one row.
+struct VmRow {
+  VmDev* (*dev)(ovh_ctx*);
+  VmProg prog;
+};
+#define VM_ROW(member, ...) \
+  VmRow { [](ovh_ctx* c) { return &c->member; }, VM_PROG(__VA_ARGS__) }
+static const VmRow VM_TABLE[] = {
+    VM_ROW(vm_vote, VOTE, VM_VOTE_SIDE),
+    VM_ROW(vm_vote_t, VOTE_T, VM_VOTE_T_SIDE),
+    VM_ROW(vm_fold, FOLD),
+    VM_ROW(vm_final, FINAL),
+    VM_ROW(vm_rs, RS),
+    VM_ROW(vm_sigchk, SIGCHK),
+    VM_ROW(vm_pkchk, PKCHK),
+    VM_ROW(vm_vote1, VOTE1),
+    VM_ROW(vm_vote_t1, VOTE_T1),
+    VM_ROW(vm_signg0, SIGNG0),
+    VM_ROW(vm_signg1, SIGNG1),
+    VM_ROW(vm_pkgen, PKGEN),
+    VM_ROW(vm_vote1h, VOTE1H),
+    VM_ROW(vm_vote_t1h, VOTE_T1H),
+    VM_ROW(vm_qcpre, QCPRE),
+    VM_ROW(vm_qcmil, QCMIL),
+    VM_ROW(vm_votew, VOTEW),
+    VM_ROW(vm_votew_t, VOTEW_T),
+    VM_ROW(vm_votewh, VOTEWH),
+    VM_ROW(vm_votewh_t, VOTEWH_T),
+    VM_ROW(vm_signg0h, SIGNG0H),
+    VM_ROW(vm_final1, FINAL1),
+    VM_ROW(vm_vsame, VSAME),
+    VM_ROW(vm_vsame_t, VSAME_T),
+    VM_ROW(vm_vsame8, VSAME8),
+    VM_ROW(vm_vsame8_t, VSAME8_T),
+    VM_ROW(vm_h2g, H2G),
+    VM_ROW(vm_gfin, GFIN),
+    VM_ROW(vm_g1grp, G1GRP),
+    VM_ROW(vm_pkdec, PKDEC),
+    VM_ROW(vm_gmil, GMIL),
+    VM_ROW(vm_g1padd, G1PADD),
+    VM_ROW(vm_madd, MADD),
+    VM_ROW(vm_padd, PADD),
+    VM_ROW(vm_hdbl[0], HDBL1),
+    VM_ROW(vm_hdbl[1], HDBL2),
+    VM_ROW(vm_hdbl[2], HDBL4),
+    VM_ROW(vm_hdbl[3], HDBL8),
+    VM_ROW(vm_hdbl[4], HDBL16),
+};
+// rs and gmil store their results from the program (vm::Out): their kernels read no output map,
+// and the generated ones are empty
+static_assert(VM_RS_NOUT == 0 && VM_GMIL_NOUT == 0, "rs / gmil: no slot outputs (tools/fpvm/progs.py)");
+
+static int vm_upload(ovh_ctx* c, VmDev& d, const VmProg& p) {
   // + PREFETCH trailing NOP phases (instruction prefetch)
-  const size_t words = (size_t)nphases * W * NW, pad = (size_t)vm::PREFETCH * W * NW;
+  const size_t words = (size_t)p.nphases * p.W * p.NW, pad = (size_t)vm::PREFETCH * p.W * p.NW;
   void *dc = nullptr, *di = nullptr, *dout = nullptr;
   HIPCHK(hipMalloc(&dc, (words + pad) * 4));
   c->vm_bufs.push_back(dc);
-  HIPCHK(hipMemcpy(dc, code, words * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dc, p.code, words * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemset((uint32_t*)dc + words, 0, pad * 4));
-  HIPCHK(hipMalloc(&di, nin * 2 + 2));
+  HIPCHK(hipMalloc(&di, p.nin * 2 + 2));
   c->vm_bufs.push_back(di);
-  HIPCHK(hipMemcpy(di, in, nin * 2, hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&dout, nout * 2 + 2));
+  HIPCHK(hipMemcpy(di, p.in, p.nin * 2, hipMemcpyHostToDevice));
+  HIPCHK(hipMalloc(&dout, p.nout * 2 + 2));
   c->vm_bufs.push_back(dout);
-  HIPCHK(hipMemcpy(dout, out, nout * 2, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dout, p.out, p.nout * 2, hipMemcpyHostToDevice));
   d.code = (const uint4*)dc;
-  d.nphases = nphases;
+  d.nphases = p.nphases;
   d.in = (const uint16_t*)di;
   d.out = (const uint16_t*)dout;
   d.trace = nullptr;
   d.clk = nullptr;
   d.side = nullptr;
-  if (side) {  // nphases x W side words + PREFETCH phases of zeros
+  if (p.side) {  // nphases x W side words + PREFETCH phases of zeros
+    const size_t sw = (size_t)p.nphases * p.W;
     void* ds = nullptr;
-    HIPCHK(hipMalloc(&ds, ((size_t)nphases + vm::PREFETCH) * W * 4));
+    HIPCHK(hipMalloc(&ds, (sw + (size_t)vm::PREFETCH * p.W) * 4));
     c->vm_bufs.push_back(ds);
-    HIPCHK(hipMemcpy(ds, side, (size_t)nphases * W * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset((uint32_t*)ds + (size_t)nphases * W, 0, (size_t)vm::PREFETCH * W * 4));
+    HIPCHK(hipMemcpy(ds, p.side, sw * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset((uint32_t*)ds + sw, 0, (size_t)vm::PREFETCH * p.W * 4));
     d.side = (const uint32_t*)ds;
   }
-  if ((c->flags & OVH_FLAG_VM_CLOCK) && (code == VM_VOTE_CODE || code == VM_VOTE_T_CODE)) {
+  if ((c->flags & OVH_FLAG_VM_CLOCK) && (p.code == VM_VOTE_CODE || p.code == VM_VOTE_T_CODE)) {
     void* dk = nullptr;
     HIPCHK(hipMalloc(&dk, (size_t)2 * VM_CLOCK_WGS * 8));
     c->vm_bufs.push_back(dk);
@@ -2836,9 +2867,9 @@ static int vm_upload(ovh_ctx* c, VmDev& d, const uint32_t* code, uint32_t nphase
   }
   if (c->flags & OVH_FLAG_VM_TRACE) {
     void* dt = nullptr;
-    HIPCHK(hipMalloc(&dt, ((size_t)nphases + 1) * 8));
+    HIPCHK(hipMalloc(&dt, ((size_t)p.nphases + 1) * 8));
     c->vm_bufs.push_back(dt);
-    HIPCHK(hipMemset(dt, 0, ((size_t)nphases + 1) * 8));
+    HIPCHK(hipMemset(dt, 0, ((size_t)p.nphases + 1) * 8));
     d.trace = (uint64_t*)dt;
   }
   return 0;
@@ -2847,93 +2878,7 @@ static int vm_upload(ovh_ctx* c, VmDev& d, const uint32_t* code, uint32_t nphase
 static int vm_init(ovh_ctx* c) {
   HIPCHK(hipMalloc(&c->vm_consts, sizeof(VM_CONST_WORDS)));
   HIPCHK(hipMemcpy(c->vm_consts, VM_CONST_WORDS, sizeof(VM_CONST_WORDS), hipMemcpyHostToDevice));
-  CHK(vm_upload(c, c->vm_vote, VM_VOTE_CODE, VM_VOTE_NPHASES, VM_VOTE_W, VM_VOTE_NW, VM_VOTE_IN, VM_VOTE_NIN, VM_VOTE_OUT,
-                VM_VOTE_NOUT,
-#if VM_VOTE_NSCR > 0
-                VM_VOTE_SIDE
-#else
-                nullptr
-#endif
-                ));
-  CHK(vm_upload(c, c->vm_vote_t, VM_VOTE_T_CODE, VM_VOTE_T_NPHASES, VM_VOTE_T_W, VM_VOTE_T_NW, VM_VOTE_T_IN, VM_VOTE_T_NIN,
-                VM_VOTE_T_OUT, VM_VOTE_T_NOUT,
-#if VM_VOTE_T_NSCR > 0
-                VM_VOTE_T_SIDE
-#else
-                nullptr
-#endif
-                ));
-  CHK(vm_upload(c, c->vm_fold, VM_FOLD_CODE, VM_FOLD_NPHASES, VM_FOLD_W, VM_FOLD_NW, VM_FOLD_IN, VM_FOLD_NIN, VM_FOLD_OUT,
-                VM_FOLD_NOUT));
-  CHK(vm_upload(c, c->vm_final, VM_FINAL_CODE, VM_FINAL_NPHASES, VM_FINAL_W, VM_FINAL_NW, VM_FINAL_IN, VM_FINAL_NIN, VM_FINAL_OUT,
-                VM_FINAL_NOUT));
-  CHK(vm_upload(c, c->vm_rs, VM_RS_CODE, VM_RS_NPHASES, VM_RS_W, VM_RS_NW, VM_RS_IN, VM_RS_NIN, VM_RS_OUT, 0));
-  CHK(vm_upload(c, c->vm_sigchk, VM_SIGCHK_CODE, VM_SIGCHK_NPHASES, VM_SIGCHK_W, VM_SIGCHK_NW, VM_SIGCHK_IN,
-                VM_SIGCHK_NIN, VM_SIGCHK_OUT, VM_SIGCHK_NOUT));
-  CHK(vm_upload(c, c->vm_pkchk, VM_PKCHK_CODE, VM_PKCHK_NPHASES, VM_PKCHK_W, VM_PKCHK_NW, VM_PKCHK_IN, VM_PKCHK_NIN,
-                VM_PKCHK_OUT, VM_PKCHK_NOUT));
-  CHK(vm_upload(c, c->vm_vote1, VM_VOTE1_CODE, VM_VOTE1_NPHASES, VM_VOTE1_W, VM_VOTE1_NW, VM_VOTE1_IN, VM_VOTE1_NIN,
-                VM_VOTE1_OUT, VM_VOTE1_NOUT));
-  CHK(vm_upload(c, c->vm_vote_t1, VM_VOTE_T1_CODE, VM_VOTE_T1_NPHASES, VM_VOTE_T1_W, VM_VOTE_T1_NW, VM_VOTE_T1_IN,
-                VM_VOTE_T1_NIN, VM_VOTE_T1_OUT, VM_VOTE_T1_NOUT));
-  CHK(vm_upload(c, c->vm_signg0, VM_SIGNG0_CODE, VM_SIGNG0_NPHASES, VM_SIGNG0_W, VM_SIGNG0_NW, VM_SIGNG0_IN,
-                VM_SIGNG0_NIN, VM_SIGNG0_OUT, VM_SIGNG0_NOUT));
-  CHK(vm_upload(c, c->vm_signg1, VM_SIGNG1_CODE, VM_SIGNG1_NPHASES, VM_SIGNG1_W, VM_SIGNG1_NW, VM_SIGNG1_IN,
-                VM_SIGNG1_NIN, VM_SIGNG1_OUT, VM_SIGNG1_NOUT));
-  CHK(vm_upload(c, c->vm_pkgen, VM_PKGEN_CODE, VM_PKGEN_NPHASES, VM_PKGEN_W, VM_PKGEN_NW, VM_PKGEN_IN, VM_PKGEN_NIN,
-                VM_PKGEN_OUT, VM_PKGEN_NOUT));
-  CHK(vm_upload(c, c->vm_vote1h, VM_VOTE1H_CODE, VM_VOTE1H_NPHASES, VM_VOTE1H_W, VM_VOTE1H_NW, VM_VOTE1H_IN,
-                VM_VOTE1H_NIN, VM_VOTE1H_OUT, VM_VOTE1H_NOUT));
-  CHK(vm_upload(c, c->vm_vote_t1h, VM_VOTE_T1H_CODE, VM_VOTE_T1H_NPHASES, VM_VOTE_T1H_W, VM_VOTE_T1H_NW, VM_VOTE_T1H_IN,
-                VM_VOTE_T1H_NIN, VM_VOTE_T1H_OUT, VM_VOTE_T1H_NOUT));
-  CHK(vm_upload(c, c->vm_qcpre, VM_QCPRE_CODE, VM_QCPRE_NPHASES, VM_QCPRE_W, VM_QCPRE_NW, VM_QCPRE_IN, VM_QCPRE_NIN,
-                VM_QCPRE_OUT, VM_QCPRE_NOUT));
-  CHK(vm_upload(c, c->vm_qcmil, VM_QCMIL_CODE, VM_QCMIL_NPHASES, VM_QCMIL_W, VM_QCMIL_NW, VM_QCMIL_IN, VM_QCMIL_NIN,
-                VM_QCMIL_OUT, VM_QCMIL_NOUT));
-  CHK(vm_upload(c, c->vm_votew, VM_VOTEW_CODE, VM_VOTEW_NPHASES, VM_VOTEW_W, VM_VOTEW_NW, VM_VOTEW_IN, VM_VOTEW_NIN,
-                VM_VOTEW_OUT, VM_VOTEW_NOUT));
-  CHK(vm_upload(c, c->vm_votew_t, VM_VOTEW_T_CODE, VM_VOTEW_T_NPHASES, VM_VOTEW_T_W, VM_VOTEW_T_NW, VM_VOTEW_T_IN,
-                VM_VOTEW_T_NIN, VM_VOTEW_T_OUT, VM_VOTEW_T_NOUT));
-  CHK(vm_upload(c, c->vm_votewh, VM_VOTEWH_CODE, VM_VOTEWH_NPHASES, VM_VOTEWH_W, VM_VOTEWH_NW, VM_VOTEWH_IN, VM_VOTEWH_NIN,
-                VM_VOTEWH_OUT, VM_VOTEWH_NOUT));
-  CHK(vm_upload(c, c->vm_votewh_t, VM_VOTEWH_T_CODE, VM_VOTEWH_T_NPHASES, VM_VOTEWH_T_W, VM_VOTEWH_T_NW, VM_VOTEWH_T_IN,
-                VM_VOTEWH_T_NIN, VM_VOTEWH_T_OUT, VM_VOTEWH_T_NOUT));
-  CHK(vm_upload(c, c->vm_signg0h, VM_SIGNG0H_CODE, VM_SIGNG0H_NPHASES, VM_SIGNG0H_W, VM_SIGNG0H_NW, VM_SIGNG0H_IN,
-                VM_SIGNG0H_NIN, VM_SIGNG0H_OUT, VM_SIGNG0H_NOUT));
-  CHK(vm_upload(c, c->vm_final1, VM_FINAL1_CODE, VM_FINAL1_NPHASES, VM_FINAL1_W, VM_FINAL1_NW, VM_FINAL1_IN,
-                VM_FINAL1_NIN, VM_FINAL1_OUT, VM_FINAL1_NOUT));
-  CHK(vm_upload(c, c->vm_vsame, VM_VSAME_CODE, VM_VSAME_NPHASES, VM_VSAME_W, VM_VSAME_NW, VM_VSAME_IN, VM_VSAME_NIN,
-                VM_VSAME_OUT, VM_VSAME_NOUT));
-  CHK(vm_upload(c, c->vm_vsame_t, VM_VSAME_T_CODE, VM_VSAME_T_NPHASES, VM_VSAME_T_W, VM_VSAME_T_NW, VM_VSAME_T_IN,
-                VM_VSAME_T_NIN, VM_VSAME_T_OUT, VM_VSAME_T_NOUT));
-  CHK(vm_upload(c, c->vm_vsame8, VM_VSAME8_CODE, VM_VSAME8_NPHASES, VM_VSAME8_W, VM_VSAME8_NW, VM_VSAME8_IN,
-                VM_VSAME8_NIN, VM_VSAME8_OUT, VM_VSAME8_NOUT));
-  CHK(vm_upload(c, c->vm_vsame8_t, VM_VSAME8_T_CODE, VM_VSAME8_T_NPHASES, VM_VSAME8_T_W, VM_VSAME8_T_NW, VM_VSAME8_T_IN,
-                VM_VSAME8_T_NIN, VM_VSAME8_T_OUT, VM_VSAME8_T_NOUT));
-  CHK(vm_upload(c, c->vm_h2g, VM_H2G_CODE, VM_H2G_NPHASES, VM_H2G_W, VM_H2G_NW, VM_H2G_IN, VM_H2G_NIN, VM_H2G_OUT,
-                VM_H2G_NOUT));
-  CHK(vm_upload(c, c->vm_gfin, VM_GFIN_CODE, VM_GFIN_NPHASES, VM_GFIN_W, VM_GFIN_NW, VM_GFIN_IN, VM_GFIN_NIN, VM_GFIN_OUT,
-                VM_GFIN_NOUT));
-  CHK(vm_upload(c, c->vm_g1grp, VM_G1GRP_CODE, VM_G1GRP_NPHASES, VM_G1GRP_W, VM_G1GRP_NW, VM_G1GRP_IN, VM_G1GRP_NIN,
-                VM_G1GRP_OUT, VM_G1GRP_NOUT));
-  CHK(vm_upload(c, c->vm_pkdec, VM_PKDEC_CODE, VM_PKDEC_NPHASES, VM_PKDEC_W, VM_PKDEC_NW, VM_PKDEC_IN, VM_PKDEC_NIN,
-                VM_PKDEC_OUT, VM_PKDEC_NOUT));
-  CHK(vm_upload(c, c->vm_gmil, VM_GMIL_CODE, VM_GMIL_NPHASES, VM_GMIL_W, VM_GMIL_NW, VM_GMIL_IN, VM_GMIL_NIN, nullptr, 0));
-  CHK(vm_upload(c, c->vm_g1padd, VM_G1PADD_CODE, VM_G1PADD_NPHASES, VM_G1PADD_W, VM_G1PADD_NW, VM_G1PADD_IN,
-                VM_G1PADD_NIN, VM_G1PADD_OUT, VM_G1PADD_NOUT));
-  CHK(vm_upload(c, c->vm_madd, VM_MADD_CODE, VM_MADD_NPHASES, VM_MADD_W, VM_MADD_NW, VM_MADD_IN, VM_MADD_NIN, VM_MADD_OUT,
-                VM_MADD_NOUT));
-  CHK(vm_upload(c, c->vm_padd, VM_PADD_CODE, VM_PADD_NPHASES, VM_PADD_W, VM_PADD_NW, VM_PADD_IN, VM_PADD_NIN, VM_PADD_OUT,
-                VM_PADD_NOUT));
-#define UPLOAD_HDBL(k, M)                                                                                               \
-  CHK(vm_upload(c, c->vm_hdbl[k], VM_HDBL##M##_CODE, VM_HDBL##M##_NPHASES, VM_HDBL##M##_W, VM_HDBL##M##_NW, VM_HDBL##M##_IN, \
-                VM_HDBL##M##_NIN, VM_HDBL##M##_OUT, VM_HDBL##M##_NOUT))
-  UPLOAD_HDBL(0, 1);
-  UPLOAD_HDBL(1, 2);
-  UPLOAD_HDBL(2, 4);
-  UPLOAD_HDBL(3, 8);
-  UPLOAD_HDBL(4, 16);
-#undef UPLOAD_HDBL
+  for (const VmRow& r : VM_TABLE) CHK(vm_upload(c, *r.dev(c), r.prog));
   HIPCHK(hipFuncSetAttribute((const void*)k_vm_pool, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_POOL));
   HIPCHK(hipFuncSetAttribute((const void*)k_vm_signg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_SIGNG));
   HIPCHK(hipFuncSetAttribute((const void*)k_vm_fold<VM_FOLD_UNITS>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -3020,6 +2965,16 @@ static void stream_park(int device, hipStream_t s) {
   g_parked.push_back(ParkedStream{device, prio, s});
 }
 
+// f(s) for every stream the context owns, ovh_stream first (destroy_one: synchronise, then park).
+template <class F>
+static void each_stream(const ovh_ctx* c, F f) {
+  for (hipStream_t s : {c->stream, c->fstream[0], c->fstream[1], c->fstream[2], c->fstream[3], c->xstream, c->vstream[0],
+                        c->vstream[1], c->vstream[2], c->pool_st[0], c->pool_st[1], c->pool_st[2], c->hstream[1],
+                        c->hstream[2], c->hstream[3], c->prime_st})
+    if (s) f(s);
+}
+static_assert(NFIN_STREAMS == 4, "each_stream names the final streams");
+
 // OVH_ERR_DEVICE once a final stream gave up waiting for the vote pool (k_pool_wait: that batch's
 // partial, verdict and codes are not trustworthy). The flag is sticky: the pool queue may still
 // hold the batch, so the context stays failed until ovh_destroy (include/ovhip.h). Every
@@ -3029,13 +2984,13 @@ static int pool_failed(const ovh_ctx* c) {
   return c->pool_err && __atomic_load_n(c->pool_err, __ATOMIC_ACQUIRE) ? OVH_ERR_DEVICE : 0;
 }
 
-// Every stream of the context idle, then the pool check above.
+// Every stream of the context that carries batch work idle, then the pool check above. Not
+// xstream (each call that uses it joins it to ovh_stream by an event) and not prime_st (the
+// message cache's next user waits for a prime, hc_touch).
 static int sync_all(ovh_ctx* c) {
   HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipStreamSynchronize(c->fstream));
-  HIPCHK(hipStreamSynchronize(c->fstream2));
-  HIPCHK(hipStreamSynchronize(c->fstream3));
-  if (c->fstream4) HIPCHK(hipStreamSynchronize(c->fstream4));
+  for (hipStream_t s : c->fstream)
+    if (s) HIPCHK(hipStreamSynchronize(s));
   for (hipStream_t s : {c->pool_st[0], c->pool_st[1], c->pool_st[2], c->vstream[0], c->vstream[1], c->vstream[2],
                         c->hstream[1], c->hstream[2], c->hstream[3]})
     if (s) HIPCHK(hipStreamSynchronize(s));
@@ -3157,8 +3112,7 @@ static int ensure_in(ovh_ctx* c, size_t bytes) {
 static int take_slot(ovh_ctx* c, int* slot) {
   const int k = (int)(c->pipe_k % OVH_BATCH_SLOTS);
   HIPCHK(hipStreamWaitEvent(c->stream, c->ev_back[k], 0));
-  const uint64_t f = c->pipe_k % c->nfin;
-  c->fs[k] = f == 0 ? c->fstream : f == 1 ? c->fstream2 : f == 2 ? c->fstream3 : c->fstream4;
+  c->fs[k] = c->fstream[c->pipe_k % c->nfin];
   ++c->pipe_k;
   c->last_slot = k;
   *slot = k;
@@ -4196,25 +4150,25 @@ static int verify_host_multi(ovh_ctx* root, size_t n, const uint8_t* sigs, const
   if (!k) return 0;
   HIPCHK(hipSetDevice(s0->device));
   for (size_t d = 0; d < nd; ++d)
-    if (dcodes[d]) HIPCHK(hipStreamWaitEvent(s0->fstream, root->sub[d]->ev_x[1], 0));
+    if (dcodes[d]) HIPCHK(hipStreamWaitEvent(s0->fstream[0], root->sub[d]->ev_x[1], 0));
   Slab uF{root->mfin, 16}, uS{root->mfin + (size_t)12 * 12 * 16, 16};
   Slab F = uF, S = uS;
   uint32_t m = (uint32_t)k;
-  k_unpack_partials<<<(uint32_t)((k * PART_PLANES + 63) / 64), 64, 0, s0->fstream>>>((uint32_t)k,
-                                                                                   (const uint32_t*)root->gather, uF, uS);
+  k_unpack_partials<<<(uint32_t)((k * PART_PLANES + 63) / 64), 64, 0, s0->fstream[0]>>>(
+      (uint32_t)k, (const uint32_t*)root->gather, uF, uS);
   if (k > 4) {
     uint32_t* o = root->mfin + (size_t)PART_PLANES * 12 * 16;
     F = Slab{o, 4};
     S = Slab{o + (size_t)12 * 12 * 4, 4};
-    k_vm_fold<VM_FOLD_UNITS><<<1, 64, LDS_FOLD, s0->fstream>>>((uint32_t)k, s0->vm_fold, s0->vm_consts, uF, uS, F,
-                                                             nullptr);
+    k_vm_fold<VM_FOLD_UNITS><<<1, 64, LDS_FOLD, s0->fstream[0]>>>((uint32_t)k, s0->vm_fold, s0->vm_consts, uF, uS, F,
+                                                                nullptr);
     m = (uint32_t)((k + 3) / 4);
   }
-  enqueue_final(s0, s0->fstream, F, S, m, s0->result + RES_MULTI);
+  enqueue_final(s0, s0->fstream[0], F, S, m, s0->result + RES_MULTI);
   HIPCHK(hipGetLastError());
   int32_t verdict = 0;
-  HIPCHK(hipMemcpyAsync(&verdict, s0->result + RES_MULTI, 4, hipMemcpyDeviceToHost, s0->fstream));
-  HIPCHK(hipStreamSynchronize(s0->fstream));
+  HIPCHK(hipMemcpyAsync(&verdict, s0->result + RES_MULTI, 4, hipMemcpyDeviceToHost, s0->fstream[0]));
+  HIPCHK(hipStreamSynchronize(s0->fstream[0]));
   std::vector<std::vector<int32_t>> staged(nd);
   for (size_t d = 0; d < nd; ++d) {
     if (!dcodes[d]) continue;
@@ -4426,7 +4380,7 @@ static int submit_host_multi(ovh_ctx* root, size_t n, const uint8_t* sigs, const
   // the combined check on the batch's final device
   HIPCHK(hipSetDevice(F->device));
   // consecutive batches' combined checks alternate between the final device's two final streams
-  const hipStream_t fin = (root->hb_k & 1) ? F->fstream2 : F->fstream;
+  const hipStream_t fin = F->fstream[root->hb_k & 1];
   for (const Part& p : ps) HIPCHK(hipStreamWaitEvent(fin, p.s->ev_m[j][p.pi], 0));
   Slab PF, PS;
   uint32_t m;
@@ -4577,13 +4531,9 @@ ovh_ctx* ovh_create(int device, const uint8_t* dst, size_t dst_len, uint32_t fla
   // draw from the high-priority set and ovh_stream from the normal one. A fifth stream of one
   // priority shares a queue and runs in order behind another.
   // a DST of more than 255 bytes is refused here (xmd_build_templates takes the whole size_t)
-  bool ok = xmd_build_templates(c->xmd, dst, dst_len) &&
-            stream_new(&c->stream, 0) == hipSuccess &&
-            stream_new(&c->fstream, lo) == hipSuccess &&
-            stream_new(&c->fstream2, lo) == hipSuccess &&
-            stream_new(&c->fstream3, lo) == hipSuccess &&
-            (c->nfin < 4 || stream_new(&c->fstream4, lo) == hipSuccess) &&
-            stream_new(&c->pool_st[0], hi) == hipSuccess &&
+  bool ok = xmd_build_templates(c->xmd, dst, dst_len) && stream_new(&c->stream, 0) == hipSuccess;
+  for (uint32_t k = 0; ok && k < std::max(3u, c->nfin); ++k) ok = stream_new(&c->fstream[k], lo) == hipSuccess;
+  ok = ok && stream_new(&c->pool_st[0], hi) == hipSuccess &&
             stream_new(&c->pool_st[1], hi) == hipSuccess &&
             (c->shard_streams < 3 || stream_new(&c->pool_st[2], hi) == hipSuccess) &&
             hipMalloc(&c->part_out, (size_t)OVH_BATCH_SLOTS * 2 * 216 * 4) == hipSuccess && hipMalloc(&c->result, RES_WORDS * 4) == hipSuccess &&
@@ -4601,7 +4551,7 @@ ovh_ctx* ovh_create(int device, const uint8_t* dst, size_t dst_len, uint32_t fla
   // NFIN_STREAMS finals in flight at most (the pool's holes hold them; r02i ran one final stream
   // per slot and lost 2.4 ms in every third vote kernel to a workgroup that found no LDS beside
   // them)
-  for (int k = 0; ok && k < OVH_BATCH_SLOTS; ++k) c->fs[k] = c->fstream;
+  for (int k = 0; ok && k < OVH_BATCH_SLOTS; ++k) c->fs[k] = c->fstream[0];
   for (int k = 0; ok && k < OVH_BATCH_SLOTS; ++k)
     ok = hipEventCreateWithFlags(&c->ev_front[k], hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&c->ev_back[k], hipEventDisableTiming) == hipSuccess;
@@ -4686,10 +4636,7 @@ int ovh_multi_peer_matrix(ovh_ctx* c, uint8_t* out, size_t cap) {
 
 static void destroy_one(ovh_ctx* c) {
   (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (hipStream_t s : {c->fstream, c->fstream2, c->fstream3, c->fstream4, c->xstream, c->vstream[0], c->vstream[1], c->vstream[2], c->pool_st[0],
-                        c->pool_st[1], c->pool_st[2], c->hstream[1], c->hstream[2], c->hstream[3], c->prime_st})
-    if (s) (void)hipStreamSynchronize(s);
+  each_stream(c, [](hipStream_t s) { (void)hipStreamSynchronize(s); });
   if (c->prime_slab) (void)hipFree(c->prime_slab);
   for (hipEvent_t e : {c->prime_ev0, c->prime_ev})
     if (e) (void)hipEventDestroy(e);
@@ -4726,10 +4673,7 @@ static void destroy_one(ovh_ctx* c) {
     if (c->vev1[k]) (void)hipEventDestroy(c->vev1[k]);
   }
   // the streams are parked, not destroyed (stream_new)
-  for (hipStream_t s : {c->stream, c->fstream, c->fstream2, c->fstream3, c->fstream4, c->xstream, c->vstream[0], c->vstream[1], c->vstream[2],
-                        c->pool_st[0], c->pool_st[1], c->pool_st[2], c->hstream[1], c->hstream[2], c->hstream[3],
-                        c->prime_st})
-    stream_park(c->device, s);
+  each_stream(c, [c](hipStream_t s) { stream_park(c->device, s); });
   if (c->pool_err) (void)hipHostFree(c->pool_err);
   delete c;
 }
