@@ -198,6 +198,63 @@ int hx_g2_mul_xabs_xy(const uint8_t* xy192, uint8_t* out192) {
   return 0;
 }
 
+// The one-lane tower and pairing (bls/tower.hpp, bls/pairing.hpp) on crafted operands
+// (tests/pairing_cases.py). An Fp12 is its 12 Fp coefficients (c0.c0.c0, c0.c0.c1, c0.c1.c0, ...)
+// as 48-byte BE canonical values. -1: a coefficient >= p; -2: an unknown op.
+static bool ld_fps(Fp* r, const uint8_t* in, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!fp_from_be48_masked(r[i], in + 48 * i, false)) return false;
+  return true;
+}
+static void st_f12(uint8_t* out576, const Fp12& f) {
+  const Fp* c = &f.c0.c0.c0;
+  for (int i = 0; i < 12; ++i) fp_to_be48(out576 + 48 * i, c[i]);
+}
+
+// op 0: a * b; 1: a^2 (fp12_sqr); 2: fp12_cyc_sqr; 3: fp12_frob; 4: fp12_inv; 5: fp12_cyc_exp_x;
+// 6: final_exponentiation. b is read by op 0 only.
+int hx_fp12_op(int op, const uint8_t* a576, const uint8_t* b576, uint8_t* out576) {
+  Fp12 a, b, r;
+  if (!ld_fps(&a.c0.c0.c0, a576, 12)) return -1;
+  switch (op) {
+    case 0:
+      if (!ld_fps(&b.c0.c0.c0, b576, 12)) return -1;
+      fp12_mul(r, a, b);
+      break;
+    case 1: fp12_sqr(r, a); break;
+    case 2: fp12_cyc_sqr(r, a); break;
+    case 3: fp12_frob(r, a); break;
+    case 4: fp12_inv(r, a); break;
+    case 5: fp12_cyc_exp_x(r, a); break;
+    case 6: final_exponentiation(r, a); break;
+    default: return -2;
+  }
+  st_f12(out576, r);
+  return 0;
+}
+
+// f * (l0 + l1 v + l4 v w); l288 = l0.c0, l0.c1, l1.c0, l1.c1, l4.c0, l4.c1
+int hx_fp12_mul_by_014(const uint8_t* f576, const uint8_t* l288, uint8_t* out576) {
+  Fp12 f;
+  Fp2 l[3];
+  if (!ld_fps(&f.c0.c0.c0, f576, 12) || !ld_fps(&l[0].c0, l288, 6)) return -1;
+  fp12_mul_by_014(f, l[0], l[1], l[2]);
+  st_f12(out576, f);
+  return 0;
+}
+
+// miller_loop(P, Q), both affine: p96 = x, y; q192 = x.c0, x.c1, y.c0, y.c1
+int hx_miller_loop(const uint8_t* p96, const uint8_t* q192, uint8_t* out576) {
+  G1A p;
+  G2A q;
+  Fp12 f;
+  if (!ld_fps(&p.x, p96, 1) || !ld_fps(&p.y, p96 + 48, 1) || !ld_fps(&q.x.c0, q192, 2) || !ld_fps(&q.y.c0, q192 + 96, 2))
+    return -1;
+  miller_loop(f, p, q);
+  st_f12(out576, f);
+  return 0;
+}
+
 // The VM's modular inverse (fpvm.hpp fp_inv) on a raw canonical value: r3 = raw R turns the
 // closing Montgomery product into the identity, so out = a^-1 mod p (0 -> 0).
 void hx_fp_inv_raw(const uint32_t* a, const uint32_t* r_raw, uint32_t* out) {
