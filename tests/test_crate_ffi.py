@@ -8,6 +8,7 @@ float -> f32, `const T*` -> `*const T`, `T*` / `T out[k]` -> `*mut T`), and the 
 the crate's error constants equal the header's. The trait surface it implements is the
 reference's `Crypto` impl (consensus.rs:385-463): the five method names are checked in lib.rs.
 """
+import glob
 import os
 import re
 
@@ -150,3 +151,57 @@ def test_cargo_dependencies_are_used_and_build_writes_out_dir():
     assert 'rerun-if-changed={}", src.join("csrc").display()' not in build
     hip = open(os.path.join(ROOT, "consensus_overlord_amd", "csrc", "ovhip.hip")).read()
     assert "#include <vm_progs.inc>" in hip   # found through -I (OUT_DIR or csrc), not beside the file
+
+
+def _unit_files():
+    """The files of the translation unit: csrc/ovhip.hip and what its quoted includes reach,
+    recursively (resolved against the including file's directory, then csrc, as hipcc -Icsrc does).
+    <...> includes and the OVH_VM_PROGS switch are not followed."""
+    csrc = os.path.join(ROOT, "consensus_overlord_amd", "csrc")
+    seen, todo = set(), [os.path.join(csrc, "ovhip.hip")]
+    while todo:
+        path = todo.pop()
+        if path in seen:
+            continue
+        seen.add(path)
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), flags=re.M):
+            for base in (os.path.dirname(path), csrc):
+                cand = os.path.normpath(os.path.join(base, inc))
+                if os.path.isfile(cand):
+                    todo.append(cand)
+                    break
+    return sorted(seen)
+
+
+def test_both_builds_track_every_file_of_the_unit():
+    """A change to any file of the translation unit rebuilds the crate's library (a
+    rerun-if-changed entry of build.rs names the file or a directory above it) and libovhip.so (the
+    file is a prerequisite of it in the Makefile)."""
+    pkg = os.path.join(ROOT, "consensus_overlord_amd")
+    own = (os.path.join(pkg, "csrc") + os.sep, os.path.join(ROOT, "include") + os.sep)
+    files = [f for f in _unit_files() if f.startswith(own)]
+    for reached in ("csrc/qc_segments.hpp", "csrc/bls/fp.hpp", "../include/ovhip.h"):  # the walk recurses
+        assert os.path.normpath(os.path.join(pkg, reached)) in files, reached
+
+    build = open(os.path.join(ROOT, "overlord-hip", "build.rs")).read()
+    listed = re.search(r"for f in \[([^\]]*)\]\s*\{\s*println!\(\"cargo:rerun-if-changed=", build)
+    assert listed, "build.rs: the `for f in [...]` list of rerun-if-changed sources not found"
+    watched = re.findall(r'"([^"]+)"', listed.group(1))
+    watched += re.findall(r'rerun-if-changed=\{\}", src\.join\("([^"]+)"\)', build)
+    watched = [os.path.normpath(os.path.join(pkg, w)) for w in watched]
+
+    make = open(os.path.join(pkg, "Makefile")).read()
+    rule = re.search(r"^libovhip\.so:(.*)$", make, flags=re.M)
+    assert rule and {"$(SRC)", "$(HDR)"} <= set(rule.group(1).split()), "libovhip.so: $(SRC) $(HDR) expected"
+    # SRC and HDR as make expands them: every `:=` / `+=` line, $(wildcard ...) calls through glob
+    words = " ".join(re.findall(r"^(?:SRC|HDR)\s*[:+]?=(.*)$", make, flags=re.M))
+    assert words.strip(), "no SRC / HDR assignment found in the Makefile"
+    pats = " ".join(re.findall(r"\$\(wildcard ([^)]*)\)", words)).split()
+    plain = re.sub(r"\$\([^)]*\)", " ", words).split()
+    prereq = [p for pat in pats for p in glob.glob(os.path.join(pkg, pat))] + [os.path.join(pkg, w) for w in plain]
+    prereq = {os.path.normpath(p) for p in prereq}
+
+    for f in files:
+        rel = os.path.relpath(f, ROOT)
+        assert any(f == w or f.startswith(w + os.sep) for w in watched), "build.rs does not watch " + rel
+        assert f in prereq, "not a prerequisite of libovhip.so: " + rel
