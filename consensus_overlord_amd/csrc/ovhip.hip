@@ -356,7 +356,7 @@ __global__ __launch_bounds__(64) void k_prime_scatter(uint32_t k, PrimeEnts ent,
 constexpr uint32_t VSAME_NSLOTS = VM_VSAME_NSLOTS > VM_VSAME_T_NSLOTS ? VM_VSAME_NSLOTS : VM_VSAME_T_NSLOTS;
 constexpr uint32_t VSAME_STRIDE_W = align256w(VSAME_NSLOTS * 12 + 4);
 // the 8-lane forms (programs vsame8 / vsame8_t: eight votes per wave) for batches of at least
-// VSAME8_MIN votes: 1,504 phases per eight votes against 1,288 per four, so a large batch's
+// VSAME8_MIN votes: 1,448 phases per eight votes against 1,288 per four, so a large batch's
 // per-vote waves take ~40% less SIMD time while a small one keeps the 16-lane form's latency
 constexpr uint32_t VSAME8_NSLOTS = VM_VSAME8_NSLOTS > VM_VSAME8_T_NSLOTS ? VM_VSAME8_NSLOTS : VM_VSAME8_T_NSLOTS;
 constexpr uint32_t VSAME8_STRIDE_W = align256w(VSAME8_NSLOTS * 12 + 4);

@@ -11,7 +11,8 @@ from vm_helpers import P, R, assert_same, build_all, golden_vote_inputs, load_go
 
 FLAGS = ("pk_ok", "pk_grp", "sig_ok", "sig_grp", "h_inf", "ok")
 SINGLE = ("pkchk", "pkdec", "sigchk")
-WHOLE = ("vote", "vote_t", "vote1", "vote1h", "votew", "votewh", "vsame", "qcpre")
+WHOLE = ("vote", "vote_t", "vote1", "vote1h", "votew", "votewh", "vsame", "qcpre", "vsame_t", "vsame8", "vsame8_t")
+NO_KEY = ("vote_t", "qcpre", "vsame_t", "vsame8_t")   # the key is a validator-table point, or the QC's sum
 SCALAR = {"vote1": 1, "vote1h": 1}
 RLC = 0xA5C3E1F00F1E3C5B
 _sims = {}
@@ -48,8 +49,9 @@ def _run(lib, device, any_all, name, key, inp, scalar=0):
 # that a renamed output fails here instead of dropping a comparison.
 ST_Q = tuple("st:q%d" % k for k in range(4))
 KEY_OUT = {"pkchk": (True, ("p0", "p1")), "pkdec": (False, None), "vote": (True, None), "vote1": (True, None),
-           "vote1h": (True, None), "votew": (True, None), "votewh": (True, None), "vsame": (True, None)}
-SIG_OUT = {"sigchk": ("q0", "q1", "q2", "q3"), "vote": ST_Q, "vote_t": ST_Q, "vsame": ST_Q, "vote1": None,
+           "vote1h": (True, None), "votew": (True, None), "votewh": (True, None), "vsame": (True, None), "vsame8": (True, None)}
+SIG_OUT = {"sigchk": ("q0", "q1", "q2", "q3"), "vote": ST_Q, "vote_t": ST_Q, "vsame": ST_Q, "vsame_t": ST_Q, "vsame8": ST_Q,
+           "vsame8_t": ST_Q, "vote1": None,
            "vote1h": None, "votew": None, "votewh": None, "qcpre": None}
 
 

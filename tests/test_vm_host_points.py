@@ -34,7 +34,7 @@ def test_vote_programs_on_one_case_per_class(hx, name, any_all):  # noqa: F811
     sigs = {s.cls for _, s in pairs if s is not None}
     assert keys == set(pc.G1_CLASSES) - {"x_ge_p"} and sigs == set(pc.G2_CLASSES) - {"x_ge_p"}
     n = point_vm.run_whole(hx, False, name, any_all)
-    assert n == (len(pairs) if name not in ("vote_t", "qcpre") else len(sigs))
+    assert n == (len(pairs) if name not in point_vm.NO_KEY else len(sigs))
 
 
 def test_norm_method_sqrt_on_g2_cases():

@@ -788,7 +788,7 @@ PROGRAMS["vsame_t"] = (build_vsame(True), VSAME_T_IN, VSAME_T_OUT)
 PROGRAMS["h2g"] = (build_h2g, H2G_IN, H2G_OUT)
 PROGRAMS["gmil"] = (build_gmil, GMIL_IN, [])
 # the same vote programs on 8-lane slices (eight votes per wave) for large same-message batches:
-# 1,504 phases per eight votes against 1,288 per four (per vote -40% on gen.py's cost model);
+# 1,448 phases per eight votes against 1,288 per four (per vote -40% on gen.py's cost model);
 # the 16-lane form keeps the shorter per-vote latency for small batches (ovhip.hip VSAME8_MIN)
 PROGRAMS["vsame8"] = (build_vsame(False), VSAME_IN, VSAME_OUT)
 PROGRAMS["vsame8_t"] = (build_vsame(True), VSAME_T_IN, VSAME_T_OUT)
