@@ -443,6 +443,16 @@ class ConsensusCrypto:
             first.setdefault(g, i)
         return [(tuple(votes[first[g]]),) + q for g, q in enumerate(qcs)], codes, taken, group
 
+    ROUNDS_MAX = 16            # include/ovhip.h OVH_ROUNDS_MAX
+    ROUND_VOTES_MAX = 1 << 24  # include/ovhip.h OVH_ROUND_VOTES_MAX
+
+    def open_round(self, hash_: bytes) -> "Round":
+        """A round on the device (ovh_round_open): build_qc for votes that arrive in several
+        flushes. Round.add verifies and adds the new votes only; the QC of everything added so far
+        is read without a second pass over the quorum. Needs update_pubkeys, which also closes
+        every open round."""
+        return Round(self, hash_)
+
     def build_proof(self, height: int, round_: int, block_hash: bytes, signatures, voters) -> bytes:
         """The overlord Proof of a block from the round's precommits: the vote hash
         hash(rlp(Vote{height, round, Precommit, block_hash})), build_qc over it, and the Proof's
@@ -540,3 +550,97 @@ class ConsensusCrypto:
             for (j, _, _, _), c in zip(items, codes):
                 ok[j] = c == 0
         return ok
+
+
+class Round:
+    """One open round of a ConsensusCrypto (ovh_round_open .. ovh_round_close): the votes on one
+    hash, added as they arrive. For any cut of a vote list into consecutive adds the codes, the
+    taken flags, the count, the bitmap and the aggregated signature equal build_qc's over the
+    whole list. Use as a context manager, or close() it; update_pubkeys closes it as well (every
+    later call then raises ValueError)."""
+
+    def __init__(self, crypto: ConsensusCrypto, hash_: bytes):
+        self.crypto = crypto
+        self.lib = crypto.lib
+        self.hash = bytes(hash_)
+        self.bitmap_len = (len(crypto.pubkeys) + 7) // 8
+        rid = ctypes.c_uint64(0)
+        raise_for(self.lib.ovh_round_open(crypto.ctx.ptr, self.hash, len(self.hash), ctypes.byref(rid)))
+        self.id: Optional[int] = int(rid.value)
+
+    def _id(self) -> int:
+        if self.id is None:
+            raise ValueError("the round is closed")
+        return self.id
+
+    def add_raw(self, signatures, voters, want_qc: bool = False):
+        """ovh_round_add without raising on its return code: (code, codes int32[n], taken bool[n],
+        n_signed, aggregated_signature or None, bitmap or None). The signature and the bitmap are
+        asked for only with want_qc (the signature is None while nothing is taken)."""
+        n = len(signatures)
+        if len(voters) != n:
+            raise Other("signatures length does not match voters length")
+        sig = b"".join(bytes(s) for s in signatures)
+        pk = b"".join(bytes(v) for v in voters)
+        if len(sig) != 96 * n or len(pk) != 48 * n:
+            raise ValueError("Round.add takes 96-byte signatures and 48-byte voters")
+        codes = np.zeros(max(n, 1), dtype=np.int32)
+        taken = np.zeros(max(n, 1), dtype=np.uint8)
+        cnt = ctypes.c_uint32(0)
+        bl = self.bitmap_len
+        out = ctypes.create_string_buffer(96) if want_qc else None
+        bitmap = ctypes.create_string_buffer(max(bl, 1)) if want_qc else None
+        code = self.lib.ovh_round_add(self.crypto.ctx.ptr, self._id(), n, sig, pk, codes.ctypes.data_as(ctypes.c_void_p),
+                                      taken.ctypes.data_as(ctypes.c_void_p), ctypes.byref(cnt), out, bitmap,
+                                      bl if want_qc else 0)
+        ok = code == OK
+        return (code, codes[:n], taken[:n].astype(bool), int(cnt.value),
+                out.raw if ok and want_qc and cnt.value else None, bitmap.raw[:bl] if ok and want_qc else None)
+
+    def add(self, signatures, voters, want_qc: bool = False):
+        """Verify the new votes on the round's hash, select, and add the taken signatures to the
+        round's sum, in one device pass over these votes only. Returns (codes, taken, n_signed):
+        codes[i] the verify_signature result of vote i (also entered in the verdict cache), taken
+        bool[n], n_signed the round's cumulative count. With want_qc -- pass it when this add is
+        expected to cross the threshold -- (codes, taken, n_signed, aggregated_signature, bitmap)
+        of everything added so far, in the same pass; the signature is None while nothing is taken."""
+        code, codes, taken, cnt, sig, bitmap = self.add_raw(signatures, voters, want_qc)
+        raise_for(code)
+        return (codes, taken, cnt, sig, bitmap) if want_qc else (codes, taken, cnt)
+
+    def qc_raw(self):
+        """ovh_round_qc: (code, aggregated_signature or None, bitmap, n_signed); code is 0, or 4
+        while nothing is taken. Anything else raises."""
+        bl = self.bitmap_len
+        out = ctypes.create_string_buffer(96)
+        bitmap = ctypes.create_string_buffer(max(bl, 1))
+        cnt = ctypes.c_uint32(0)
+        code = self.lib.ovh_round_qc(self.crypto.ctx.ptr, self._id(), out, bitmap, bl, ctypes.byref(cnt))
+        if code not in (OK, 4):
+            raise_for(code)
+        return code, (out.raw if code == OK else None), bitmap.raw[:bl], int(cnt.value)
+
+    def qc(self):
+        """The QC of what has been added so far, with no verification: (aggregated_signature,
+        bitmap, n_signed). Raises CryptoErr(4) while nothing is taken, as build_qc does."""
+        code, agg, bitmap, cnt = self.qc_raw()
+        raise_for(code)
+        return agg, bitmap, cnt
+
+    def close(self) -> None:
+        """ovh_round_close. Closing twice, or a round that update_pubkeys closed, is no error."""
+        rid, self.id = self.id, None
+        if rid is not None and getattr(self.crypto.ctx, "ptr", None):
+            self.lib.ovh_round_close(self.crypto.ctx.ptr, rid)
+
+    def __enter__(self) -> "Round":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -1602,6 +1602,24 @@ struct ValidatorTable {
   std::vector<uint32_t> sorted;                     // entries by key bytes (overlord authority order)
 };
 
+// An open round (ovh_round_open; qc.hpp has the layout of `dev`). The selection indexes the
+// entries of the table the round was opened on: ovh_set_validators closes every round.
+struct QcRound {
+  uint64_t id = 0;
+  uint8_t hash[32] = {};
+  uint64_t base = 0;        // votes added so far
+  uint32_t* dev = nullptr;  // owner (tn) | bitmap (bw) | count | merged | pad | R (72 words) | 96 QC bytes
+  uint32_t tn = 0, bw = 0;
+  uint32_t* owner() const { return dev; }
+  uint32_t* bitmap() const { return dev + tn; }
+  uint32_t* count() const { return dev + tn + bw; }
+  uint32_t* merged() const { return dev + tn + bw + 1; }
+  static size_t r_off(uint32_t tn, uint32_t bw) { return ((size_t)tn + bw + 2 + 15) / 16 * 16; }
+  uint32_t* R() const { return dev + r_off(tn, bw); }
+  uint8_t* out96() const { return (uint8_t*)(R() + 6 * 12); }  // ovh_round_qc's compressed R
+  static size_t words(uint32_t tn, uint32_t bw) { return r_off(tn, bw) + 6 * 12 + 96 / 4; }
+};
+
 // Verdict cache of ovh_prefetch: exact (sig, hash, voter) bytes -> per-vote code.
 struct VerdictCache {
   std::mutex mu;
@@ -1696,6 +1714,13 @@ struct ovh_ctx {
   // RLC coefficients: fresh getrandom seed per batch, or the test seed (OVH_FLAG_TEST_RLC)
   uint64_t test_seed = 0, test_base = 0;
   ValidatorTable tab;
+  std::vector<QcRound> rounds;  // open rounds, at most OVH_ROUNDS_MAX (a multi context's: on sub[0])
+  uint64_t round_next = 1;      // ids are never reused
+  // ovh_round_add of up to small_max votes: sigma of the add's votes from a sigchk launch on
+  // xstream, beside the verify (S_SIG + 6 planes of rsig_cap entries: the sum reads a vote's
+  // sigma at plane S_SIG, as in a batch slot's state). One add at a time uses it (c->mu).
+  uint32_t* rsig = nullptr;
+  uint32_t rsig_cap = 0;
   uint32_t* qc_buf = nullptr;  // QC batch: apk planes + flags
   uint32_t qc_cap = 0;
   uint32_t* qt_buf = nullptr;  // explicit-key QC (ovh_verify_aggregated): decoded keys + flags
@@ -3120,6 +3145,46 @@ static int verify_samemsg_locked(ovh_ctx* c, int slot, size_t n, const uint8_t* 
   return 0;
 }
 
+// The two parts of a batch staged table-first, outside the same-message route: the table votes
+// [0, t), then the others [t, n), each a batch of its own (verify_async_locked) with its codes at
+// dc + its first vote. hashes: the caller's host bytes, vote j's at 32 perm[j]. dhent: room for n
+// message-table entries in the staging image; hent: their host source, which must live until the
+// caller has synchronised. slots (may be null): the batch slot each part ran in, -1 for an empty
+// part -- ev_back[slot] is recorded behind the part's last kernel.
+static int verify_parts_locked(ovh_ctx* c, size_t n, uint8_t* d, size_t t, const std::vector<uint32_t>& perm,
+                               const uint8_t* hashes, int32_t* dc, uint32_t* dhent, std::vector<uint32_t>& hent,
+                               int* slots = nullptr) {
+  for (int part = 0; part < 2; ++part) {  // table votes [0, t), then the others [t, n)
+    const size_t lo = part ? t : 0, cnt = part ? n - t : t;
+    if (slots) slots[part] = -1;
+    if (!cnt) continue;
+    // a part of 2 .. small_max votes whose hashes are all in the message table (ovh_prime_hashes,
+    // or seen by the per-call verify) runs k_vm_votewh on the table's H: no hash_to_field, no
+    // hash_to_G2 per vote. VOTEWH_MAX: its waves are co-resident. The entries travel in the
+    // staging image, in the votes' staged order.
+    const uint32_t* d_hent = nullptr;
+    if (c->prime_batch && c->hc_planes && cnt >= 2 && cnt <= c->small_max && cnt <= VOTEWH_MAX) {
+      hent.resize(n);
+      bool all = true;
+      std::string hk;
+      for (size_t j = lo; j < lo + cnt && all; ++j) {
+        hk.assign((const char*)hashes + 32 * (perm.empty() ? j : perm[j]), 32);
+        all = hc_find(c, hk, &hent[j]);
+      }
+      if (all) {
+        CHK(hc_touch(c));
+        uint32_t* dh = dhent + lo;
+        HIPCHK(hipMemcpyAsync(dh, hent.data() + lo, 4 * cnt, hipMemcpyHostToDevice, c->stream));
+        d_hent = dh;
+        ++c->prime_parts;
+      }
+    }
+    CHK(verify_async_locked(c, cnt, d + 96 * lo, d + n * 96 + 32 * lo, staged_key(c, n, d, t, lo), dc + lo, d_hent));
+    if (slots) slots[part] = c->last_slot;
+  }
+  return 0;
+}
+
 // ovh_verify_batch on one device (caller holds c->mu): codes (host) of n votes. Table votes and
 // the others run as two batches (each its own combined check) when a batch mixes them.
 static int verify_host_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* hashes, const uint8_t* pks,
@@ -3162,32 +3227,7 @@ static int verify_host_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const u
   } else if (n == 1) {
     CHK(verify_one_locked(c, d, d + 96, staged_key(c, n, d, t, 0), dc, hashes));
   } else {
-    for (int part = 0; part < 2; ++part) {  // table votes [0, t), then the others [t, n)
-      const size_t lo = part ? t : 0, cnt = part ? n - t : t;
-      if (!cnt) continue;
-      // a part of 2 .. small_max votes whose hashes are all in the message table (ovh_prime_hashes,
-      // or seen by the per-call verify) runs k_vm_votewh on the table's H: no hash_to_field, no
-      // hash_to_G2 per vote. VOTEWH_MAX: its waves are co-resident. The entries travel in the
-      // staging image, in the votes' staged order.
-      const uint32_t* d_hent = nullptr;
-      if (c->prime_batch && c->hc_planes && cnt >= 2 && cnt <= c->small_max && cnt <= VOTEWH_MAX) {
-        hent.resize(n);
-        bool all = true;
-        std::string hk;
-        for (size_t j = lo; j < lo + cnt && all; ++j) {
-          hk.assign((const char*)hashes + 32 * (perm.empty() ? j : perm[j]), 32);
-          all = hc_find(c, hk, &hent[j]);
-        }
-        if (all) {
-          CHK(hc_touch(c));
-          uint32_t* dh = (uint32_t*)(d + n * 184) + lo;
-          HIPCHK(hipMemcpyAsync(dh, hent.data() + lo, 4 * cnt, hipMemcpyHostToDevice, c->stream));
-          d_hent = dh;
-          ++c->prime_parts;
-        }
-      }
-      CHK(verify_async_locked(c, cnt, d + 96 * lo, d + n * 96 + 32 * lo, staged_key(c, n, d, t, lo), dc + lo, d_hent));
-    }
+    CHK(verify_parts_locked(c, n, d, t, perm, hashes, dc, (uint32_t*)(d + n * 184), hent));
   }
   CHK(sync_all(c));
   if (perm.empty()) {
@@ -3778,9 +3818,10 @@ static void destroy_one(ovh_ctx* c) {
                   (void*)c->pool_scr, (void*)c->plog, (void*)c->vm_consts,
                   (void*)c->fin, (void*)c->scr, (void*)c->scr_pk, (void*)c->scr_sig, (void*)c->comb,
                   (void*)c->tab.planes, (void*)c->tab.flags, (void*)c->tab.qc, (void*)c->tab.qcg, (void*)c->qc_buf, (void*)c->qt_buf, (void*)c->hc_planes, (void*)c->hc_inf, (void*)c->gather,
-                  (void*)c->mfin, (void*)c->sm1_plan, (void*)c->sm1_hash})
+                  (void*)c->mfin, (void*)c->sm1_plan, (void*)c->sm1_hash, (void*)c->rsig})
     if (p) (void)hipFree(p);
   for (void* p : c->vm_bufs) (void)hipFree(p);
+  for (const QcRound& r : c->rounds) (void)hipFree(r.dev);
   for (int k = 0; k < OVH_BATCH_SLOTS; ++k)
     for (hipEvent_t e : {c->ev_front[k], c->ev_back[k]})
       if (e) (void)hipEventDestroy(e);
@@ -4551,6 +4592,9 @@ int ovh_verify_aggregated(ovh_ctx* c, const uint8_t* agg_sig, size_t agg_len, co
 static int set_validators_locked(ovh_ctx* c, const uint8_t* pks, size_t n) {
   HIPCHK(hipSetDevice(c->device));
   CHK(sync_all(c));
+  // the rounds' owner words index the old table's entries: every open round is closed
+  for (const QcRound& r : c->rounds) (void)hipFree(r.dev);
+  c->rounds.clear();
   ValidatorTable& t = c->tab;
   uint32_t cap = 64;
   while (cap < n) cap <<= 1;
@@ -5109,15 +5153,17 @@ static int ensure_qc_cap(ovh_ctx* c, size_t n, const QcSegments& sg) {
 }
 
 // The selection (qc.hpp) over n staged votes, the first t of them of table voters (a table of tn
-// entries) -> owner, bitmap, count and taken of `sel`.
-static void enqueue_qc_select(hipStream_t st, uint32_t tn, uint32_t n, uint32_t t, const QcSel& sel) {
-  k_qc_reset<<<nblk((size_t)sel.groups * tn), WG, 0, st>>>(tn, sel);
+// entries) -> owner, bitmap, count and taken of `sel`. reset false: against a live round, whose
+// words keep what its earlier adds claimed and marked (sel.base).
+static void enqueue_qc_select(hipStream_t st, uint32_t tn, uint32_t n, uint32_t t, const QcSel& sel, bool reset = true) {
+  if (reset) k_qc_reset<<<nblk((size_t)sel.groups * tn), WG, 0, st>>>(tn, sel);
   if (t) k_qc_claim<<<nblk(t), WG, 0, st>>>(tn, t, sel);
   k_qc_mark<<<nblk(n), WG, 0, st>>>(tn, n, t, sel);
 }
 
 // The masked G2 sum (qc.hpp) of the taken sigma of n >= 2 votes in a.st, and its compression.
-// sg null: one sum over all votes -> a.A[0] -> 96 bytes at out96. Else one sum per group of the
+// sg null: one sum over all votes -> a.A[0] -> 96 bytes at out96 (null: the sum stays projective
+// in a.A[0], for a round's merge). Else one sum per group of the
 // segment layout sg (dlist, dseg: its list and segment table on the device) -> a.A[32 seg[2 g]]
 // -> 96 bytes per group.
 static void enqueue_qc_sum(ovh_ctx* c, hipStream_t st, const MsmArgs& a, uint32_t n, const uint32_t* dtaken,
@@ -5133,8 +5179,22 @@ static void enqueue_qc_sum(ovh_ctx* c, hipStream_t st, const MsmArgs& a, uint32_
     k_qc_chunk<false><<<(n + MSM_CH - 1) >> MSM_CH_LV, 64, LDS_MSM8, st>>>(n, dtaken, nullptr, c->vm_madd, c->vm_padd,
                                                                           MSM8_STRIDE_W, c->vm_consts, a);
     if (n > MSM_CH) k_qc_upper<false><<<1, 64, LDS_MSM8, st>>>(n, nullptr, c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
-    k_g2p_compress<<<1, 64, 0, st>>>(a.A, out96);
+    if (out96) k_g2p_compress<<<1, 64, 0, st>>>(a.A, out96);
   }
+}
+
+// The side sigma slab of a round's small adds (ovh_ctx::rsig). Nothing is in flight on it: every
+// add synchronises before it returns.
+static int ensure_rsig(ovh_ctx* c, size_t n) {
+  if (c->rsig && n <= c->rsig_cap) return 0;
+  uint32_t cap = 64;
+  while (cap < n) cap <<= 1;
+  if (c->rsig) (void)hipFree(c->rsig);
+  c->rsig = nullptr;
+  c->rsig_cap = 0;
+  HIPCHK(hipMalloc(&c->rsig, (size_t)(S_SIG + 6) * 12 * cap * 4));
+  c->rsig_cap = cap;
+  return 0;
 }
 
 // ovh_build_qc on one device (caller holds c->mu, the table is set): the round's verify batch on
@@ -5151,17 +5211,31 @@ static void enqueue_qc_sum(ovh_ctx* c, hipStream_t st, const MsmArgs& a, uint32_
 // (qc_segments.hpp), one k_qc_upper workgroup and one compression per group; the host renumbers
 // the groups by first appearance in the caller's order when it writes the outputs. The single
 // outputs (out_sig, bitmap, n_signed) are unused then.
+//
+// ovh_round_add (rd set): the same pass over the new votes against the
+// round's own owner / bitmap / count words, with no reset and claims offset by rd->base; the
+// add's sum stays projective in the slot's tree and k_qc_merge folds it into the round's R, which
+// is compressed only when out_sig is given. An add of 2 .. small_max votes is verified as
+// ovh_prefetch verifies a batch of that size (verify_parts_locked), then sigchk supplies sigma. bitmap and out_sig may be null, the counts are the
+// round's cumulative ones, and an add that takes nothing is no error.
 static int build_qc_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* hashes, const uint8_t* pks,
                            int32_t* codes, uint8_t* taken, uint8_t* out_sig, uint8_t* bitmap, size_t bitmap_len,
-                           uint32_t* n_signed, const QcGroupsOut* mo = nullptr) {
+                           uint32_t* n_signed, const QcGroupsOut* mo = nullptr, const QcRound* rd = nullptr) {
   HIPCHK(hipSetDevice(c->device));
   const ValidatorTable& tb = c->tab;
   const uint32_t N = (uint32_t)n;
   std::vector<uint32_t> perm;
   std::vector<int32_t> tidx;
   const size_t t = table_split(c, n, pks, perm, tidx);
+  // A round's add of 2 .. small_max votes takes the route ovh_prefetch takes at that size (the
+  // small-batch path, on the message table's H when the hash is there): its latency is below the
+  // same-message route's, which a trickle of flushes pays once per flush. That path keeps no
+  // sigma (nor does the per-call check of one vote), so one sigchk launch without the subgroup
+  // check supplies them: on xstream into the context's side slab, beside the verify.
+  const bool small = rd && n >= 2 && n <= c->small_max && c->samemsg < 2;
+  const bool side = rd && (n == 1 || small);
   SameMsgPlan pl;
-  if (n >= 2) samemsg_plan(n, hashes, perm, pl);
+  if (n >= 2 && !small) samemsg_plan(n, hashes, perm, pl);
   const uint32_t G = mo ? pl.G : 1, bw = (tb.n + 31) / 32;
   QcSegments sg;
   if (mo) {  // the group count is decided here, before any device work
@@ -5170,12 +5244,18 @@ static int build_qc_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint
   }
   const size_t lbytes = 4 * (sg.list.size() + sg.seg.size());
   // staging: sigs | (hashes) | pks | codes | table indices, the plan (and the segment list and
-  // table), then orig | taken | a zero offset and a code word (sigchk) | 96 output bytes per group
+  // table; a small add: the message-table entries), then orig | taken | sigchk's offsets and code
+  // words (one vote, or a small add's n) | 96 output bytes per group
   pl.off = (n * (96 + 32 + 48 + 4 + 4) + 255) / 256 * 256;
-  const size_t qoff = (pl.off + pl.bytes + lbytes + 255) / 256 * 256;
-  const size_t zoff = qoff + 8 * n, ooff = zoff + 16;
+  const size_t qoff = (pl.off + (small ? 4 * n : pl.bytes + lbytes) + 255) / 256 * 256;
+  const size_t ns = small ? n : 1;
+  const size_t zoff = qoff + 8 * n, ooff = zoff + 16 * ns;
   CHK(ensure_in(c, ooff + 96 * (size_t)G));
   CHK(ensure_qc_cap(c, n, sg));
+  if (side) {
+    CHK(ensure_rsig(c, n));
+    if (!c->xstream) HIPCHK(stream_new(&c->xstream, 0));
+  }
   if (mo) CHK(ensure_qcg(c, (size_t)G * ((size_t)tb.n + bw + 1)));
   uint8_t* d = c->in_buf;
   int32_t* dc = (int32_t*)(d + n * 176);
@@ -5183,20 +5263,22 @@ static int build_qc_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint
   uint32_t* dorig = (uint32_t*)(d + qoff);
   uint32_t* dtaken = dorig + n;
   std::vector<uint8_t> hb, hp;
+  std::vector<uint32_t> hent;
+  std::vector<uint64_t> soff;
   std::vector<int32_t> pc(n);
   std::vector<uint32_t> ptk(n), cnts(G, 0), hbm(mo ? (size_t)G * bw : 0);
   std::vector<uint8_t> sig96(96 * (size_t)G);
   // an error return drains the streams that copy from / into the host buffers above before they
   // die; the normal return has waited already (the call's one synchronisation)
   struct Drain {
-    hipStream_t s[2];
+    hipStream_t s[3];
     bool armed;
     ~Drain() {
       if (armed)
         for (hipStream_t x : s)
           if (x) (void)hipStreamSynchronize(x);
     }
-  } drain{{c->stream, nullptr}, true};
+  } drain{{c->stream, nullptr, nullptr}, true};
   if (perm.empty()) {
     HIPCHK(hipMemcpyAsync(d, sigs, n * 96, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(d + n * 128, pks, n * 48, hipMemcpyHostToDevice, c->stream));
@@ -5213,12 +5295,39 @@ static int build_qc_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint
   if (t) HIPCHK(hipMemcpyAsync(d + n * 180, tidx.data(), t * 4, hipMemcpyHostToDevice, c->stream));
   int slot;
   hipStream_t st;
+  const Slab rsigma{side ? c->rsig + (size_t)S_SIG * 12 * c->rsig_cap : nullptr, c->rsig_cap};
+  if (side) {
+    // sigma of every staged vote (projective with Z = 1, so the affine planes the sum reads are
+    // the first four; the identity for a signature that does not parse, whose vote is never
+    // taken), as soon as the signatures are staged: the verify below does not wait for it
+    constexpr uint32_t SL = 64 / VM_SIGCHK_W;
+    soff.resize(n);
+    for (size_t j = 0; j < n; ++j) soff[j] = 96 * j;
+    HIPCHK(hipMemcpyAsync(d + zoff, soff.data(), 8 * n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(c->ev_x[2], c->stream));  // staged inputs
+    HIPCHK(hipStreamWaitEvent(c->xstream, c->ev_x[2], 0));
+    drain.s[2] = c->xstream;
+    k_vm_sigchk<<<(N + SL - 1) / SL, 64, LDS_SIGCHK, c->xstream>>>(N, c->vm_sigchk, c->vm_consts, d,
+                                                                   (const uint64_t*)(d + zoff), 0,
+                                                                   (int32_t*)(d + zoff + 8 * n), rsigma);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_x[3], c->xstream));
+  }
   if (n == 1) {
-    HIPCHK(hipMemsetAsync(d + zoff, 0, 16, c->stream));  // sigchk's offset word
+    if (!side) HIPCHK(hipMemsetAsync(d + zoff, 0, 16, c->stream));  // sigchk's offset word
     HIPCHK(hipMemcpyAsync(d + 96, hashes, 32, hipMemcpyHostToDevice, c->stream));
     CHK(verify_one_locked(c, d, d + 96, staged_key(c, n, d, t, 0), dc, hashes));
     slot = c->last_slot;
     st = c->stream;
+  } else if (small) {
+    // every vote signs the round's hash: the rows need no permutation
+    HIPCHK(hipMemcpyAsync(d + n * 96, hashes, n * 32, hipMemcpyHostToDevice, c->stream));
+    int ps[2];
+    CHK(verify_parts_locked(c, n, d, t, perm, hashes, dc, (uint32_t*)(d + pl.off), hent, ps));
+    // the sum runs on the last part's final stream, behind the other part's as well
+    slot = ps[1] >= 0 ? ps[1] : ps[0];
+    st = c->fs[slot];
+    if (ps[1] >= 0 && ps[0] >= 0) HIPCHK(hipStreamWaitEvent(st, c->ev_back[ps[0]], 0));
   } else {
     hp.resize(pl.bytes + lbytes);
     memcpy(hp.data(), pl.gid.data(), 4 * n);
@@ -5238,7 +5347,8 @@ static int build_qc_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint
     st = c->fs[slot];
   }
   uint32_t* cur;
-  const MsmArgs a = msm_args(c, slot, &cur);  // the MSM's bucket trees are done with: A holds the sum's tree
+  MsmArgs a = msm_args(c, slot, &cur);  // the MSM's bucket trees are done with: A holds the sum's tree
+  if (side) a.st = Slab{c->rsig, c->rsig_cap};
   QcSel sel;
   sel.codes = dc;
   sel.tidx = dtidx;
@@ -5252,32 +5362,48 @@ static int build_qc_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint
     sel.owner = tb.qcg;
     sel.bitmap = sel.owner + (size_t)G * tb.n;
     sel.count = sel.bitmap + (size_t)G * bw;
+  } else if (rd) {
+    sel.owner = rd->owner();
+    sel.bitmap = rd->bitmap();
+    sel.count = rd->count();
+    sel.base = (uint32_t)rd->base;
   } else {
     sel.owner = tb.qc;
     sel.bitmap = tb.qc + 2 * (size_t)tb.cap;
     sel.count = sel.bitmap + tb.cap / 32;
   }
   sel.taken = dtaken;
-  enqueue_qc_select(st, tb.n, N, (uint32_t)t, sel);
+  enqueue_qc_select(st, tb.n, N, (uint32_t)t, sel, !rd);
+  if (side) HIPCHK(hipStreamWaitEvent(st, c->ev_x[3], 0));
   if (mo) {
     const uint32_t* dlist = (const uint32_t*)(d + pl.off + pl.bytes);
     enqueue_qc_sum(c, st, a, N, dtaken, &sg, dlist, dlist + sg.list.size(), d + ooff);
   } else if (n == 1) {
-    constexpr uint32_t SL = 64 / VM_SIGCHK_W;
-    k_vm_sigchk<<<(1 + SL - 1) / SL, 64, LDS_SIGCHK, st>>>(1, c->vm_sigchk, c->vm_consts, d, (const uint64_t*)(d + zoff), 0,
-                                                           (int32_t*)(d + zoff + 8), a.A);
-    k_g2p_compress<<<1, 64, 0, st>>>(a.A, d + ooff);
+    if (!rd) {
+      constexpr uint32_t SL = 64 / VM_SIGCHK_W;
+      k_vm_sigchk<<<(1 + SL - 1) / SL, 64, LDS_SIGCHK, st>>>(1, c->vm_sigchk, c->vm_consts, d, (const uint64_t*)(d + zoff),
+                                                             0, (int32_t*)(d + zoff + 8), a.A);
+      k_g2p_compress<<<1, 64, 0, st>>>(a.A, d + ooff);
+    }
   } else {
-    enqueue_qc_sum(c, st, a, N, dtaken, nullptr, nullptr, nullptr, d + ooff);
+    enqueue_qc_sum(c, st, a, N, dtaken, nullptr, nullptr, nullptr, rd ? nullptr : d + ooff);
+  }
+  if (rd) {
+    MsmArgs m = a;
+    if (n == 1) m.A = rsigma;  // the one vote's sigma
+    m.U = Slab{rd->R(), 1};
+    k_qc_merge<<<1, 64, LDS_MSM8, st>>>(sel.count, rd->merged(), n == 1 ? dtaken : nullptr, c->vm_padd, MSM8_STRIDE_W,
+                                        c->vm_consts, m);
+    if (out_sig) k_g2p_compress<<<1, 64, 0, st>>>(m.U, d + ooff);
   }
   HIPCHK(hipGetLastError());
   drain.s[1] = st;
   HIPCHK(hipMemcpyAsync(pc.data(), dc, 4 * n, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(ptk.data(), dtaken, 4 * n, hipMemcpyDeviceToHost, st));
   if (mo) HIPCHK(hipMemcpyAsync(hbm.data(), sel.bitmap, 4 * hbm.size(), hipMemcpyDeviceToHost, st));
-  else HIPCHK(hipMemcpyAsync(bitmap, sel.bitmap, bitmap_len, hipMemcpyDeviceToHost, st));
+  else if (bitmap) HIPCHK(hipMemcpyAsync(bitmap, sel.bitmap, bitmap_len, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(cnts.data(), sel.count, 4 * (size_t)G, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(sig96.data(), d + ooff, sig96.size(), hipMemcpyDeviceToHost, st));
+  if (out_sig || mo) HIPCHK(hipMemcpyAsync(sig96.data(), d + ooff, sig96.size(), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   drain.armed = false;
   CHK(pool_failed(c));
@@ -5308,6 +5434,10 @@ static int build_qc_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint
     return 0;
   }
   *n_signed = cnts[0];
+  if (rd) {
+    if (out_sig && cnts[0]) memcpy(out_sig, sig96.data(), 96);
+    return 0;
+  }
   if (!cnts[0]) return BLST_AGGR_TYPE_MISMATCH;
   memcpy(out_sig, sig96.data(), 96);
   return 0;
@@ -5358,6 +5488,112 @@ int ovh_build_qcs(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* hash
   }
   if (r == 0) cache_put(c, n, sigs, hashes, pks, codes);
   return r;
+}
+
+// Rounds. The rounds of a context live on the device context that runs
+// them (a multi context's first), under its mutex.
+static QcRound* round_find(ovh_ctx* s, uint64_t id) {
+  for (QcRound& r : s->rounds)
+    if (r.id == id) return &r;
+  return nullptr;
+}
+static void round_drop(ovh_ctx* s, uint64_t id) {
+  for (size_t k = 0; k < s->rounds.size(); ++k)
+    if (s->rounds[k].id == id) {
+      (void)hipFree(s->rounds[k].dev);
+      s->rounds.erase(s->rounds.begin() + k);
+      return;
+    }
+}
+
+int ovh_round_open(ovh_ctx* c, const uint8_t* hash, size_t hash_len, uint64_t* round) {
+  if (!c || !hash || !round) return OVH_ERR_ARG;
+  if (hash_len != 32) return OVH_ERR_HASH_LEN;
+  ovh_ctx* s = c->sub.empty() ? c : c->sub[0];
+  std::lock_guard<std::mutex> g(s->mu);
+  if (!s->tab.n || s->rounds.size() >= OVH_ROUNDS_MAX) return OVH_ERR_ARG;
+  HIPCHK(hipSetDevice(s->device));
+  // H(hash) into the message table, ahead of the votes: the adds of one vote and of a few then
+  // skip hash_to_G2 (as after ovh_prime_hashes; no wait here)
+  CHK(prime_locked(s, 1, hash));
+  QcRound r;
+  r.tn = s->tab.n;
+  r.bw = (s->tab.n + 31) / 32;
+  memcpy(r.hash, hash, 32);
+  HIPCHK(hipMalloc(&r.dev, QcRound::words(r.tn, r.bw) * 4));
+  QcSel sel{};
+  sel.groups = 1;
+  sel.bw = r.bw;
+  sel.owner = r.owner();
+  sel.bitmap = r.bitmap();
+  sel.count = r.count();
+  k_qc_reset<<<nblk(r.tn), WG, 0, s->stream>>>(r.tn, sel);
+  k_qc_rinit<<<1, 64, 0, s->stream>>>(r.merged(), Slab{r.R(), 1});
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess) {
+    (void)hipFree(r.dev);
+    return OVH_ERR_DEVICE;
+  }
+  r.id = s->round_next++;
+  s->rounds.push_back(r);
+  *round = r.id;
+  return 0;
+}
+
+int ovh_round_add(ovh_ctx* c, uint64_t round, size_t n, const uint8_t* sigs, const uint8_t* pks, int32_t* codes,
+                  uint8_t* taken, uint32_t* n_signed, uint8_t* out_sig, uint8_t* bitmap, size_t bitmap_len) {
+  if (!c || !sigs || !pks || !codes || !n_signed) return OVH_ERR_ARG;
+  if (n == 0 || n > OVH_ROUND_VOTES_MAX) return OVH_ERR_ARG;
+  std::vector<uint8_t> hashes(n * 32);  // the batch's and the verdict cache's per-vote form
+  int r;
+  {
+    ovh_ctx* s = c->sub.empty() ? c : c->sub[0];
+    std::lock_guard<std::mutex> g(s->mu);
+    QcRound* rd = round_find(s, round);
+    if (!rd || rd->base + n > OVH_ROUND_VOTES_MAX) return OVH_ERR_ARG;
+    if (bitmap && bitmap_len != ((size_t)s->tab.n + 7) / 8) return OVH_ERR_ARG;
+    for (size_t i = 0; i < n; ++i) memcpy(&hashes[32 * i], rd->hash, 32);
+    r = build_qc_locked(s, n, sigs, hashes.data(), pks, codes, taken, out_sig, bitmap, bitmap_len, n_signed, nullptr, rd);
+    if (r == 0) rd->base += n;
+    else round_drop(s, round);  // a device or RNG error: the round's words and R may be half updated
+  }
+  if (r == 0) cache_put(c, n, sigs, hashes.data(), pks, codes);
+  return r;
+}
+
+int ovh_round_qc(ovh_ctx* c, uint64_t round, uint8_t out_sig[96], uint8_t* bitmap, size_t bitmap_len,
+                 uint32_t* n_signed) {
+  if (!c || !out_sig || !bitmap || !n_signed) return OVH_ERR_ARG;
+  ovh_ctx* s = c->sub.empty() ? c : c->sub[0];
+  std::lock_guard<std::mutex> g(s->mu);
+  const QcRound* rd = round_find(s, round);
+  if (!rd || bitmap_len != ((size_t)s->tab.n + 7) / 8) return OVH_ERR_ARG;
+  HIPCHK(hipSetDevice(s->device));
+  uint32_t cnt = 0;
+  uint8_t sig96[96];
+  // the stream copies into the locals above and the caller's bitmap: an error return waits for it first
+  struct Drain {
+    hipStream_t s;
+    ~Drain() { (void)hipStreamSynchronize(s); }
+  } drain{s->stream};
+  k_g2p_compress<<<1, 64, 0, s->stream>>>(Slab{rd->R(), 1}, rd->out96());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(&cnt, rd->count(), 4, hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipMemcpyAsync(bitmap, rd->bitmap(), bitmap_len, hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipMemcpyAsync(sig96, rd->out96(), 96, hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  *n_signed = cnt;
+  if (!cnt) return BLST_AGGR_TYPE_MISMATCH;
+  memcpy(out_sig, sig96, 96);
+  return 0;
+}
+
+int ovh_round_close(ovh_ctx* c, uint64_t round) {
+  if (!c) return OVH_ERR_ARG;
+  ovh_ctx* s = c->sub.empty() ? c : c->sub[0];
+  std::lock_guard<std::mutex> g(s->mu);
+  if (!round_find(s, round)) return OVH_ERR_ARG;
+  round_drop(s, round);
+  return 0;
 }
 
 int ovh_set_test_rlc(ovh_ctx* c, uint64_t seed, uint64_t index_base) {

@@ -10,6 +10,8 @@
 //   k_qc_upper   the levels above, one workgroup over the chunk sums (loops over the pairs of a
 //                level, so the launch count does not grow with log2 n)
 //   k_qc_compress the groups' sums to 96 bytes each (ovh_build_qcs)
+//   k_qc_rinit   a round's running sum to the identity (ovh_round_open)
+//   k_qc_merge   a round's running sum += one add's sum (ovh_round_add)
 // The sum reads the sigma planes the same-message vote program left in the state slab (affine,
 // decompressed and subgroup-checked once); a vote that is not taken contributes the identity.
 // The kernels keep the MSM kernels' rules: no workgroup waits for another, the levels of a
@@ -36,6 +38,10 @@ struct QcSel {
   uint32_t* bitmap;      // MSB-first bytes, written as words
   uint32_t* count;
   uint32_t* taken;       // per staged vote: 1 or 0
+  // ovh_round_add: the votes the round took in before this call. A claim is base + the caller's
+  // index, so one of an earlier add (below base) beats every claim of this one, and the owner
+  // words are not reset between adds. 0: a selection that stands alone.
+  uint32_t base = 0;
 };
 
 __global__ __launch_bounds__(WG) void k_qc_reset(uint32_t tn, QcSel s) {
@@ -49,7 +55,7 @@ __global__ __launch_bounds__(WG) void k_qc_claim(uint32_t tn, uint32_t t, QcSel 
   const uint32_t j = blockIdx.x * WG + threadIdx.x;
   if (j < t && s.codes[j] == 0) {
     const uint32_t g = s.gid ? s.gid[j] : 0u;
-    atomicMin(&s.owner[g * tn + (uint32_t)s.tidx[j]], s.orig ? s.orig[j] : j);
+    atomicMin(&s.owner[g * tn + (uint32_t)s.tidx[j]], s.base + (s.orig ? s.orig[j] : j));
   }
 }
 
@@ -60,7 +66,7 @@ __global__ __launch_bounds__(WG) void k_qc_mark(uint32_t tn, uint32_t n, uint32_
   if (j < t && s.codes[j] == 0) {
     const uint32_t e = (uint32_t)s.tidx[j];
     if (s.gid) g = s.gid[j];
-    tk = s.owner[g * tn + e] == (s.orig ? s.orig[j] : j);
+    tk = s.owner[g * tn + e] == s.base + (s.orig ? s.orig[j] : j);
     if (tk) {
       const uint32_t k = s.rank[e];  // bit k: byte k / 8, MSB first (little-endian words)
       atomicOr(&s.bitmap[g * s.bw + (k >> 5)], 1u << (8 * ((k >> 3) & 3) + 7 - (k & 7)));
@@ -159,4 +165,36 @@ __global__ __launch_bounds__(64) void k_qc_upper(uint32_t n, const uint32_t* __r
 __global__ __launch_bounds__(64) void k_qc_compress(Slab in, const uint32_t* __restrict__ seg, uint8_t* out) {
   if (threadIdx.x) return;
   g2p_compress(in, seg[2 * blockIdx.x] << (MSM_CH_LV - 1), out + 96 * (size_t)blockIdx.x);
+}
+
+// Rounds (ovh_round_open / _add / _qc). A round's state is one allocation:
+// owner (tn words) | bitmap (bw) | count | merged, then -- from the next 16-word boundary -- the
+// running sum R, a projective G2 point stored as a one-entry slab (72 words). `merged` is the
+// count that R stands for: an add whose selection took nothing leaves count == merged.
+__global__ __launch_bounds__(64) void k_qc_rinit(uint32_t* merged, Slab R) {
+  const uint32_t c = threadIdx.x;
+  if (c == 0) *merged = 0;
+  if (c >= 6) return;
+  Fp v;
+  if (c == 2) fp_one(v);  // (0 : 1 : 0)
+  else fp_zero(v);
+  R.st(v, c, 0);
+}
+
+// R <- R + (this add's sum): a.U is the round's R (one entry), a.A[0] the sum that k_qc_chunk /
+// k_qc_upper left in the slot's tree or, for an add of one vote, its sigma from k_vm_sigchk. One
+// pair on the first slice of one one-wave workgroup. padd is the complete addition, which the merge needs:
+// R is the identity until the first taken vote, the sums of two adds can be equal (a doubling) or
+// opposite (the identity again), and none of these may take another path than the generic pair.
+// The gate is here, not on the host: nothing is added when the add took no vote (`taken1`, the
+// one vote's taken word, when the add has one vote; else the count against `merged`).
+__global__ __launch_bounds__(64) void k_qc_merge(const uint32_t* __restrict__ count, uint32_t* merged,
+                                                 const uint32_t* __restrict__ taken1, VmDev padd, uint32_t stride_w,
+                                                 const uint32_t* __restrict__ cst_g, MsmArgs a) {
+  constexpr uint32_t W = VM_PADD_W;
+  const uint32_t cnt = *count;
+  if (taken1 ? taken1[0] == 0 : cnt == *merged) return;  // uniform; merged is written behind the barriers below
+  MSM_VM_PROLOGUE(W);
+  msm_pair_op<W>(padd, VM_PADD_NIN, slots, cst, lane, slice == 0, a, SRC_U, 0, SRC_A, 0, SRC_U, 0);
+  if (threadIdx.x == 0) *merged = cnt;
 }

@@ -27,6 +27,15 @@ with its signed hash since the last flush, the shim primes that hash at once
 hash_to_G2 of the hash runs while the rest of the group arrives, and the flush's batch runs on
 the cached H.
 
+Rounds (opt-in, `rounds=True`): a leader wants the QC the moment the count crosses its threshold,
+and votes reach it in several flushes. With the option, a flush hands the fixed-size SignedVotes
+of each signed hash, in arrival order, to that hash's device round (`ConsensusCrypto.open_round`
+-> `Round.add`, which verifies the new votes only, fills the verdict cache as prefetch does, and
+adds the taken signatures to the round's running sum) in place of `prefetch`; chokes and every
+other encoding go to `prefetch` as before. `VoteIngress.qc(hash)` reads the round's QC with no
+second pass over the quorum. Rounds are opened on first use; when ROUNDS_MAX are open the one
+opened first is closed.
+
 Wire layouts [dep: overlord 0.4 types + rlp 0.5, not vendored; named assumption 7 in DESIGN.md]:
   SignedVote   = rlp([signature bytes, Vote, voter bytes])
   Vote         = rlp([height u64, round u64, vote_type u8, block_hash bytes])  (vote.rlp_vote)
@@ -41,6 +50,7 @@ from __future__ import annotations
 import logging
 import time
 from dataclasses import dataclass
+from collections import OrderedDict
 from typing import Callable, Dict, List, Optional, Tuple
 
 from . import vote as _v
@@ -52,6 +62,7 @@ AGGREGATED_VOTE = "AggregatedVote"
 SIGNED_PROPOSAL = "SignedProposal"
 SIGNED_CHOKE = "SignedChoke"
 CHOKE_KIND = 2          # group key kind of a choke (vote kinds are PREVOTE 0 / PRECOMMIT 1)
+ROUNDS_MAX = 16         # include/ovhip.h OVH_ROUNDS_MAX: device rounds open per context
 
 
 @dataclass(frozen=True)
@@ -143,10 +154,11 @@ class _Pending:
 class VoteIngress:
     """proc_network_msg with vote batching. `crypto`: a ConsensusCrypto (prefetch, hash,
     vote_digests, pubkeys); `forward(kind, msg)`: hands a decoded message to overlord
-    (overlord_handler.send_msg, consensus.rs:214-253)."""
+    (overlord_handler.send_msg, consensus.rs:214-253). `rounds=True` (and a crypto with
+    open_round): a flush's votes go to the device round of their signed hash (module docstring)."""
 
     def __init__(self, crypto, forward: Callable[[str, object], None], batch_size: Optional[int] = None,
-                 max_delay_s: float = 0.002, clock: Callable[[], float] = time.monotonic):
+                 max_delay_s: float = 0.002, clock: Callable[[], float] = time.monotonic, rounds: bool = False):
         self.crypto = crypto
         self.forward = forward
         self.batch_size = batch_size
@@ -156,6 +168,10 @@ class VoteIngress:
         self.groups: Dict[Tuple[int, int, int], int] = {}
         self.primed: set = set()    # signed hashes primed since the last flush
         self.stats = {"batches": 0, "prefetched": 0, "forwarded": 0, "dropped": 0, "unbatched": 0}
+        self.use_rounds = bool(rounds) and hasattr(crypto, "open_round")
+        self.rounds: "OrderedDict[bytes, object]" = OrderedDict()   # signed hash -> Round, oldest first
+        if self.use_rounds:
+            self.stats.update({"round_adds": 0, "round_votes": 0})
 
     def _limit(self) -> int:
         if self.batch_size:
@@ -230,6 +246,8 @@ class VoteIngress:
         # other encodings go to overlord as they are: its verify_signature takes the exact
         # per-call path (a cache miss)
         self.stats["unbatched"] += len(items) - len(fixed)
+        if self.use_rounds:
+            fixed = self._add_to_rounds(items, hs, fixed)
         if fixed:
             self.crypto.prefetch([items[k].signature for k in fixed], [hs[k] for k in fixed],
                                  [items[k].voter for k in fixed])
@@ -237,6 +255,40 @@ class VoteIngress:
             self.stats["prefetched"] += len(fixed)
         for p in items:
             self._send(p.kind, p.msg)
+
+    def _round(self, h: bytes):
+        r = self.rounds.get(h)
+        if r is None:
+            if len(self.rounds) >= ROUNDS_MAX:
+                self.rounds.popitem(last=False)[1].close()   # the round opened first
+            r = self.rounds[h] = self.crypto.open_round(h)
+        return r
+
+    def _add_to_rounds(self, items, hs, fixed) -> List[int]:
+        """The fixed-size SignedVotes among `fixed`, grouped by signed hash in arrival order, go to
+        their rounds; returns what is left for prefetch."""
+        groups: "OrderedDict[bytes, List[int]]" = OrderedDict()
+        rest = []
+        for k in fixed:
+            if items[k].kind == SIGNED_VOTE:
+                groups.setdefault(hs[k], []).append(k)
+            else:
+                rest.append(k)
+        for h, ks in groups.items():
+            self._round(h).add([items[k].signature for k in ks], [items[k].voter for k in ks])
+            self.stats["round_adds"] += 1
+            self.stats["round_votes"] += len(ks)
+        return rest
+
+    def qc(self, hash_: bytes):
+        """The QC of the votes on `hash_` flushed so far (Round.qc: aggregated signature, bitmap,
+        n_signed). KeyError when no round is open on the hash; rounds=True only."""
+        return self.rounds[bytes(hash_)].qc()
+
+    def close_rounds(self) -> None:
+        """Close every open round (a new height, or before the validator set changes)."""
+        while self.rounds:
+            self.rounds.popitem()[1].close()
 
     def _send(self, kind, msg) -> None:
         self.stats["forwarded"] += 1

@@ -320,6 +320,58 @@ int ovh_build_qcs(ovh_ctx* ctx, size_t n, const uint8_t* sigs /* n x 96 */, cons
                   uint8_t* group_hashes /* max_groups x 32 */, uint8_t* out_sigs /* max_groups x 96 */,
                   uint8_t* bitmaps /* max_groups x bitmap_len */, size_t bitmap_len, uint32_t* n_signed /* max_groups */);
 
+/* Rounds on the device: ovh_build_qc for votes that arrive in several flushes. A round keeps, in
+ * device memory, which table entries have a taken vote, the bitmap, the count and the running sum
+ * of the taken signatures; each ovh_round_add is one device pass over the new votes only, and the
+ * QC is read without a second pass over the quorum. Needs ovh_set_validators. Host buffers,
+ * synchronous, thread-safe (the context mutex, as ovh_build_qc); a multi-device context runs its
+ * rounds on its first device.
+ * The defining property: for any list of votes V on the round's hash and any cut of V into
+ * consecutive pieces V1 .. Vk (pieces of one vote included), added in order, the concatenated
+ * codes and taken equal what ovh_build_qc(V) writes, and after the last add *n_signed, the bitmap
+ * and the 96 signature bytes equal ovh_build_qc(V)'s, byte for byte. So codes[i] is exactly the
+ * ovh_verify result, and a vote is taken iff its code is 0, its voter is in the validator table
+ * and no earlier vote of that voter was taken -- earlier in this add or in any earlier add of the
+ * round. An invalid earlier vote does not block a later valid one, across adds too.
+ *   ovh_round_open   opens a round on `hash` (the SM3 of rlp(Vote), hash_len 32); *round gets a
+ *                    non-zero id that this context never reuses. At most OVH_ROUNDS_MAX are open.
+ *                    The hash is primed as by ovh_prime_hashes (no wait), so the adds find H(hash)
+ *                    in the message cache.
+ *   ovh_round_add    verifies n more votes (sigs n x 96 B, pks n x 48 B), selects, and adds the
+ *                    taken signatures to the round's sum. codes, taken (may be NULL): this add's
+ *                    votes, as ovh_build_qc's. *n_signed: the round's cumulative count. bitmap
+ *                    (may be NULL; else bitmap_len == ceil(table size / 8), checked only then):
+ *                    the cumulative bitmap, ovh_build_qc's layout. out_sig (may be NULL): the
+ *                    compressed cumulative sum, written only when *n_signed > 0 -- pass it when
+ *                    this add is expected to cross the threshold: the compression then rides in
+ *                    the same pass, behind the same single host synchronisation. The verdicts
+ *                    enter the verdict cache as ovh_build_qc's do. Returns 0 whenever the outputs
+ *                    were written, also when nothing was taken. A round accepts
+ *                    OVH_ROUND_VOTES_MAX votes over all its adds. The votes are verified as
+ *                    ovh_prefetch verifies a batch of that size: one vote per call, up to
+ *                    OVH_SMALL_MAX on the small-batch path, more on the same-message route.
+ *   ovh_round_qc     the QC of what has been added so far, without any verification: returns 0
+ *                    and out_sig, bitmap, *n_signed; BLST_AGGR_TYPE_MISMATCH (4) while nothing is
+ *                    taken (a zero bitmap and *n_signed = 0 are written, out_sig is not).
+ *   ovh_round_close  frees the round; its id is unknown from then on.
+ * Errors: OVH_ERR_HASH_LEN for hash_len != 32; OVH_ERR_ARG for a NULL required pointer, no
+ * validator table, an unknown or closed id, n == 0, an open beyond OVH_ROUNDS_MAX, an add that
+ * would take the round past OVH_ROUND_VOTES_MAX, or a wrong bitmap_len. A refused call changes
+ * nothing: the next call behaves as if it had never been made. An add that fails with a device or
+ * RNG error closes its round. ovh_set_validators closes every open round (the selection indexes
+ * table entries, so their ids go stale); ovh_destroy frees them. ovh_build_qc / ovh_build_qcs
+ * calls between the adds of a round do not disturb it. */
+#define OVH_ROUNDS_MAX 16              /* rounds open per context */
+#define OVH_ROUND_VOTES_MAX (1u << 24) /* votes a round accepts over all its adds */
+int ovh_round_open(ovh_ctx* ctx, const uint8_t* hash, size_t hash_len, uint64_t* round);
+int ovh_round_add(ovh_ctx* ctx, uint64_t round, size_t n, const uint8_t* sigs /* n x 96 */,
+                  const uint8_t* pks /* n x 48 */, int32_t* codes /* n */, uint8_t* taken /* n, may be NULL */,
+                  uint32_t* n_signed, uint8_t* out_sig /* 96, may be NULL */, uint8_t* bitmap /* may be NULL */,
+                  size_t bitmap_len);
+int ovh_round_qc(ovh_ctx* ctx, uint64_t round, uint8_t out_sig[96], uint8_t* bitmap, size_t bitmap_len,
+                 uint32_t* n_signed);
+int ovh_round_close(ovh_ctx* ctx, uint64_t round);
+
 /* TESTS ONLY (context created with OVH_FLAG_TEST_RLC, else OVH_ERR_ARG): vote i of every
  * following batch gets the coefficient SplitMix64(seed, index_base + i). Predictable
  * coefficients let an adversary cancel invalid signatures inside the combined check

@@ -38,6 +38,8 @@ pub const OVH_PARTIAL_BYTES: usize = 864;
 pub const OVH_BATCH_SLOTS: usize = 6;
 pub const OVH_QC_GROUPS_MAX: usize = 64;
 pub const OVH_PRIME_MAX: usize = 64;
+pub const OVH_ROUNDS_MAX: usize = 16;
+pub const OVH_ROUND_VOTES_MAX: usize = 1 << 24;
 
 extern "C" {
     pub fn ovh_create(device: i32, dst: *const u8, dst_len: usize, flags: u32) -> *mut OvhCtx;
@@ -71,6 +73,10 @@ extern "C" {
     pub fn ovh_verify_qc_batch(ctx: *mut OvhCtx, nq: usize, sigs: *const u8, hashes: *const u8, bitmaps: *const u8, bitmap_len: usize, codes: *mut i32) -> i32;
     pub fn ovh_build_qc(ctx: *mut OvhCtx, n: usize, sigs: *const u8, hash: *const u8, hash_len: usize, pks: *const u8, codes: *mut i32, taken: *mut u8, out_sig: *mut u8, bitmap: *mut u8, bitmap_len: usize, n_signed: *mut u32) -> i32;
     pub fn ovh_build_qcs(ctx: *mut OvhCtx, n: usize, sigs: *const u8, hashes: *const u8, pks: *const u8, codes: *mut i32, taken: *mut u8, group: *mut u32, max_groups: usize, n_groups: *mut u32, group_hashes: *mut u8, out_sigs: *mut u8, bitmaps: *mut u8, bitmap_len: usize, n_signed: *mut u32) -> i32;
+    pub fn ovh_round_open(ctx: *mut OvhCtx, hash: *const u8, hash_len: usize, round: *mut u64) -> i32;
+    pub fn ovh_round_add(ctx: *mut OvhCtx, round: u64, n: usize, sigs: *const u8, pks: *const u8, codes: *mut i32, taken: *mut u8, n_signed: *mut u32, out_sig: *mut u8, bitmap: *mut u8, bitmap_len: usize) -> i32;
+    pub fn ovh_round_qc(ctx: *mut OvhCtx, round: u64, out_sig: *mut u8, bitmap: *mut u8, bitmap_len: usize, n_signed: *mut u32) -> i32;
+    pub fn ovh_round_close(ctx: *mut OvhCtx, round: u64) -> i32;
     pub fn ovh_set_test_rlc(ctx: *mut OvhCtx, seed: u64, index_base: u64) -> i32;
     pub fn ovh_verify_batch_device(ctx: *mut OvhCtx, n: usize, d_sigs: *const u8, d_hashes: *const u8, d_pks: *const u8, d_codes: *mut i32) -> i32;
     pub fn ovh_batch_partial_device(ctx: *mut OvhCtx, n: usize, d_sigs: *const u8, d_hashes: *const u8, d_pks: *const u8, d_codes: *mut i32, d_partial: *mut u8, stream: *mut c_void) -> i32;

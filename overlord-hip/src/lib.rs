@@ -370,6 +370,78 @@ impl HipCrypto {
         })?;
         Ok((ok.into_iter().map(|b| b == 1).collect(), reasons))
     }
+
+    /// A round on the device (`ovh_round_open`): `build_qc` for votes that arrive in several
+    /// flushes. `hash` is the 32-byte hash the round's votes sign. The round holds the context
+    /// alive and closes itself when dropped; `update_pubkeys` closes every open round (their
+    /// later calls return `CryptoErr(OVH_ERR_ARG)`). At most `OVH_ROUNDS_MAX` are open. Blocking.
+    pub fn open_round(&self, hash: &[u8]) -> Result<Round, Box<dyn Error + Send>> {
+        let mut id = 0u64;
+        check(unsafe { ffi::ovh_round_open(self.raw(), hash.as_ptr(), hash.len(), &mut id) })?;
+        Ok(Round { ctx: self.ctx.clone(), id, bitmap_len: (self.pubkeys.blocking_read().len() + 7) / 8 })
+    }
+}
+
+/// One open round of a `HipCrypto` (`ovh_round_open` .. `ovh_round_close`). For any cut of a vote
+/// list into consecutive `add`s the codes, the taken flags, the count, the bitmap and the
+/// signature equal `build_qc`'s over the whole list.
+pub struct Round {
+    ctx: Arc<Ctx>,
+    id: u64,
+    bitmap_len: usize,
+}
+
+/// What `Round::add` returns: the per-vote codes and taken flags of this add, the round's
+/// cumulative count, and -- when asked for -- the cumulative QC (signature, bitmap); the
+/// signature is `None` while nothing is taken.
+pub type RoundAdd = (Vec<i32>, Vec<u8>, u32, Option<(Option<Bytes>, Bytes)>);
+
+impl Round {
+    /// Verify `sigs.len()` more votes on the round's hash, select, and add the taken signatures
+    /// to the round's sum, in one device pass over these votes only (`ovh_round_add`). Pass
+    /// `want_qc` when this add is expected to cross the threshold: the compression then rides
+    /// in the same pass. The verdicts enter the verdict cache. Blocking.
+    pub fn add(&self, sigs: &[[u8; 96]], voters: &[[u8; 48]], want_qc: bool) -> Result<RoundAdd, Box<dyn Error + Send>> {
+        if sigs.len() != voters.len() {
+            return Err(to_err(ffi::OVH_ERR_LEN_MISMATCH));
+        }
+        let mut codes = vec![0i32; sigs.len()];
+        let mut taken = vec![0u8; sigs.len()];
+        let mut bitmap = vec![0u8; self.bitmap_len];
+        let mut out = [0u8; 96];
+        let mut n_signed = 0u32;
+        let (po, pb) = if want_qc { (out.as_mut_ptr(), bitmap.as_mut_ptr()) } else { (std::ptr::null_mut(), std::ptr::null_mut()) };
+        check(unsafe {
+            ffi::ovh_round_add(self.ctx.0, self.id, sigs.len(), sigs.as_ptr() as *const u8, voters.as_ptr() as *const u8,
+                               codes.as_mut_ptr(), taken.as_mut_ptr(), &mut n_signed, po, pb, self.bitmap_len)
+        })?;
+        let qc = if want_qc {
+            let sig = if n_signed > 0 { Some(Bytes::copy_from_slice(&out)) } else { None };
+            Some((sig, Bytes::from(bitmap)))
+        } else {
+            None
+        };
+        Ok((codes, taken, n_signed, qc))
+    }
+
+    /// The QC of what has been added so far, without any verification (`ovh_round_qc`):
+    /// signature, bitmap, number of taken votes. `CryptoErr(4)` while nothing is taken. Blocking.
+    pub fn qc(&self) -> Result<(Bytes, Bytes, u32), Box<dyn Error + Send>> {
+        let mut bitmap = vec![0u8; self.bitmap_len];
+        let mut out = [0u8; 96];
+        let mut n_signed = 0u32;
+        check(unsafe {
+            ffi::ovh_round_qc(self.ctx.0, self.id, out.as_mut_ptr(), bitmap.as_mut_ptr(), self.bitmap_len, &mut n_signed)
+        })?;
+        Ok((Bytes::copy_from_slice(&out), Bytes::from(bitmap), n_signed))
+    }
+}
+
+impl Drop for Round {
+    fn drop(&mut self) {
+        // an id that update_pubkeys already closed is refused (OVH_ERR_ARG): nothing to do
+        unsafe { ffi::ovh_round_close(self.ctx.0, self.id) };
+    }
 }
 
 impl OverlordCrypto for HipCrypto {
