@@ -52,6 +52,8 @@ SIGNATURES = [
     ("ovh_round_open", ctypes.c_int, [_vp, _u8p, _sz, ctypes.POINTER(ctypes.c_uint64)]),
     ("ovh_round_add", ctypes.c_int, [_vp, ctypes.c_uint64, _sz, _u8p, _u8p, _vp, _vp, ctypes.POINTER(ctypes.c_uint32),
                                      _vp, _vp, _sz]),
+    ("ovh_rounds_add", ctypes.c_int, [_vp, _sz, _u8p, _vp, _u8p, _vp, _vp, _vp, _sz, ctypes.POINTER(ctypes.c_uint32),
+                                      _vp, _vp, _vp, _vp, _sz]),
     ("ovh_round_qc", ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp, _sz, ctypes.POINTER(ctypes.c_uint32)]),
     ("ovh_round_close", ctypes.c_int, [_vp, ctypes.c_uint64]),
     ("ovh_set_test_rlc", ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64]),

@@ -453,6 +453,54 @@ class ConsensusCrypto:
         every open round."""
         return Round(self, hash_)
 
+    def add_rounds_raw(self, rounds, signatures, voters, want_qc: bool = False):
+        """ovh_rounds_add without raising on its return code. rounds: one open Round per vote (the
+        round the vote is for; the vote is verified under that round's hash). Returns (code, codes
+        int32[n], taken bool[n], per_round); per_round lists the distinct rounds in order of first
+        appearance as (Round, n_signed, aggregated_signature or None, bitmap or None) -- the
+        round's cumulative count and, with want_qc only, its cumulative QC (the signature is None
+        while nothing is taken). per_round is empty when the call was refused."""
+        n = len(signatures)
+        if len(voters) != n or len(rounds) != n:
+            raise Other("signatures length does not match voters length")
+        sig = b"".join(bytes(s) for s in signatures)
+        pk = b"".join(bytes(v) for v in voters)
+        if len(sig) != 96 * n or len(pk) != 48 * n:
+            raise ValueError("add_rounds takes 96-byte signatures and 48-byte voters")
+        by_id = {}
+        for r in rounds:
+            by_id.setdefault(r._id(), r)
+        ids = np.array([r._id() for r in rounds] or [0], dtype=np.uint64)
+        mr = self.ROUNDS_MAX
+        bl = (len(self.pubkeys) + 7) // 8
+        codes = np.zeros(max(n, 1), dtype=np.int32)
+        taken = np.zeros(max(n, 1), dtype=np.uint8)
+        rid = np.zeros(mr, dtype=np.uint64)
+        cnt = np.zeros(mr, dtype=np.uint32)
+        out = np.zeros((mr, 96), dtype=np.uint8)
+        bm = np.zeros((mr, max(bl, 1)), dtype=np.uint8)
+        nr = ctypes.c_uint32(0)
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+        code = self.lib.ovh_rounds_add(self.ctx.ptr, n, sig, ptr(ids), pk, ptr(codes), ptr(taken), None, mr,
+                                       ctypes.byref(nr), ptr(rid), ptr(cnt), ptr(out) if want_qc else None,
+                                       ptr(bm) if want_qc else None, bl if want_qc else 0)
+        per_round = []
+        if code == OK:
+            for k in range(int(nr.value)):
+                per_round.append((by_id[int(rid[k])], int(cnt[k]),
+                                  out[k].tobytes() if want_qc and cnt[k] else None,
+                                  bm[k, :bl].tobytes() if want_qc else None))
+        return code, codes[:n], taken[:n].astype(bool), per_round
+
+    def add_rounds(self, rounds, signatures, voters, want_qc: bool = False):
+        """A flush's votes added to several open rounds in one device pass (ovh_rounds_add): vote i
+        goes to rounds[i]. Every round ends exactly as if Round.add had been called with the
+        sub-list of its votes, in the caller's order. Returns (codes, taken, per_round) as
+        add_rounds_raw; raises on a refused call, which changes nothing."""
+        code, codes, taken, per_round = self.add_rounds_raw(rounds, signatures, voters, want_qc)
+        raise_for(code)
+        return codes, taken, per_round
+
     def build_proof(self, height: int, round_: int, block_hash: bytes, signatures, voters) -> bytes:
         """The overlord Proof of a block from the round's precommits: the vote hash
         hash(rlp(Vote{height, round, Precommit, block_hash})), build_qc over it, and the Proof's

@@ -47,6 +47,7 @@
 #include "fpvm.hpp"
 #include "keygen.hpp"
 #include "proof.hpp"
+#include "qc_round_groups.hpp"
 #include "qc_segments.hpp"
 #include "rlp.hpp"
 #include "sm3.hpp"
@@ -5174,7 +5175,7 @@ static void enqueue_qc_sum(ovh_ctx* c, hipStream_t st, const MsmArgs& a, uint32_
                                                       c->vm_consts, a);
     if (sg->chunks > G)  // a group of more than one chunk
       k_qc_upper<true><<<G, 64, LDS_MSM8, st>>>(0, dseg, c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
-    k_qc_compress<<<G, 64, 0, st>>>(a.A, dseg, out96);
+    if (out96) k_qc_compress<<<G, 64, 0, st>>>(a.A, dseg, out96);  // null: ovh_rounds_add merges the sums instead
   } else {
     k_qc_chunk<false><<<(n + MSM_CH - 1) >> MSM_CH_LV, 64, LDS_MSM8, st>>>(n, dtaken, nullptr, c->vm_madd, c->vm_padd,
                                                                           MSM8_STRIDE_W, c->vm_consts, a);
@@ -5558,6 +5559,242 @@ int ovh_round_add(ovh_ctx* c, uint64_t round, size_t n, const uint8_t* sigs, con
   }
   if (r == 0) cache_put(c, n, sigs, hashes.data(), pks, codes);
   return r;
+}
+
+// ovh_rounds_add on one device, for n >= 2 votes over K >= 2 open rounds
+// (caller holds c->mu and has refused what is to be refused; rc.g is numbered): ovh_round_add's
+// pass with the rounds of the call side by side. One verify of all n votes under their rounds'
+// hashes -- up to small_max votes as ovh_prefetch verifies them (verify_parts_locked, sigma from
+// one sigchk launch on the side stream), more on the same-message plan over the per-vote hashes,
+// whose groups are hashes and have nothing to do with the rounds' numbers -- then, on the final
+// stream: the selection through the table of round references (claims are the round's base + the
+// vote's position among that round's votes of the call), the segmented masked sum with one
+// segment per round, the segmented merge into each round's R, the gather of counts and bitmaps
+// and, when asked for, the compression of each R. One host synchronisation.
+// The device part of ovh_rounds_add behind the verify, on stream st: n staged votes (the first t
+// of table voters) over the K = sg's groups rounds of the table drefs. sel: codes, tidx, rank,
+// taken, gid (the round numbers) and orig (the positions). dlist / dseg: sg on the device. drows:
+// K rows of count | gw bitmap words (gw 0: the counts alone). out96 (may be null): 96 bytes per
+// non-empty round. sigma_ready (may be null): the event behind which a.st holds the votes' sigma.
+static int enqueue_qc_rounds(ovh_ctx* c, hipStream_t st, const MsmArgs& a, uint32_t n, uint32_t t, const QcSel& sel,
+                             const QcRoundRef* drefs, const QcSegments& sg, const uint32_t* dlist, const uint32_t* dseg,
+                             uint32_t gw, uint32_t* drows, uint8_t* out96, hipEvent_t sigma_ready) {
+  const uint32_t K = (uint32_t)(sg.seg.size() / 2);
+  if (t) k_qc_claim_r<<<nblk(t), WG, 0, st>>>(t, sel, drefs);
+  k_qc_mark_r<<<nblk(n), WG, 0, st>>>(n, t, sel, drefs);
+  if (sigma_ready) HIPCHK(hipStreamWaitEvent(st, sigma_ready, 0));
+  enqueue_qc_sum(c, st, a, n, sel.taken, &sg, dlist, dseg, nullptr);
+  k_qc_merge_seg<<<K, 64, LDS_MSM8, st>>>(drefs, dseg, c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
+  k_qc_rgather<<<K, 64, 0, st>>>(drefs, gw, drows);
+  if (out96) k_qc_rcompress<<<K, 64, 0, st>>>(drefs, out96);
+  return 0;
+}
+
+struct QcRoundsCall {
+  QcRoundGroups* g;
+  QcRound* const* rd;  // the K rounds, by number
+  uint32_t* n_signed;
+  uint8_t* out_sigs;  // may be null
+  uint8_t* bitmaps;   // may be null
+  size_t bitmap_len;
+};
+
+static int rounds_add_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* hashes, const uint8_t* pks,
+                             int32_t* codes, uint8_t* taken, const QcRoundsCall& rc) {
+  HIPCHK(hipSetDevice(c->device));
+  const ValidatorTable& tb = c->tab;
+  const uint32_t N = (uint32_t)n, K = rc.g->K, bw = (tb.n + 31) / 32;
+  std::vector<uint32_t> perm;
+  std::vector<int32_t> tidx;
+  const size_t t = table_split(c, n, pks, perm, tidx);
+  const bool small = n <= c->small_max && c->samemsg < 2;
+  SameMsgPlan pl;
+  if (!small) samemsg_plan(n, hashes, perm, pl);
+  qc_round_stage(n, perm.empty() ? nullptr : perm.data(), *rc.g);
+  QcSegments sg;
+  qc_segments(n, K, rc.g->gid.data(), sg);
+  const uint32_t gw = rc.bitmaps ? bw : 0;  // bitmap words of a gathered row
+  // staging: sigs | hashes | pks | codes | table indices, the plan (a small call: the
+  // message-table entries), then round references | round numbers | segment list and table,
+  // then positions | taken | sigchk's offsets and code words (a small call) | gathered rows
+  // (count | bitmap words per round) | 96 output bytes per round
+  pl.off = (n * (96 + 32 + 48 + 4 + 4) + 255) / 256 * 256;
+  const size_t roff = (pl.off + (small ? 4 * n : pl.bytes) + 255) / 256 * 256;
+  const size_t rbytes = sizeof(QcRoundRef) * K + 4 * n + 4 * (sg.list.size() + sg.seg.size());
+  const size_t qoff = (roff + rbytes + 255) / 256 * 256;
+  const size_t zoff = qoff + 8 * n, goff = (zoff + (small ? 16 * n : 0) + 15) / 16 * 16;
+  const size_t ooff = goff + 4 * (size_t)K * (1 + gw);
+  CHK(ensure_in(c, ooff + 96 * (size_t)K));
+  CHK(ensure_qc_cap(c, n, sg));
+  if (small) CHK(ensure_rsig(c, n));
+  if (!c->xstream) HIPCHK(stream_new(&c->xstream, 0));
+  uint8_t* d = c->in_buf;
+  int32_t* dc = (int32_t*)(d + n * 176);
+  const int32_t* dtidx = (const int32_t*)(d + n * 180);
+  const QcRoundRef* drefs = (const QcRoundRef*)(d + roff);
+  const uint32_t* dgid = (const uint32_t*)(d + roff + sizeof(QcRoundRef) * K);
+  const uint32_t* dlist = dgid + n;
+  const uint32_t* dseg = dlist + sg.list.size();
+  uint32_t* dorig = (uint32_t*)(d + qoff);
+  uint32_t* dtaken = dorig + n;
+  uint32_t* drows = (uint32_t*)(d + goff);
+  std::vector<uint8_t> hb, hp, hr(rbytes);
+  std::vector<uint32_t> hent;
+  std::vector<uint64_t> soff;
+  std::vector<int32_t> pc(n);
+  std::vector<uint32_t> ptk(n), rows((size_t)K * (1 + gw));
+  std::vector<uint8_t> sig96(rc.out_sigs ? 96 * (size_t)K : 0);
+  {
+    QcRoundRef* ref = (QcRoundRef*)hr.data();
+    for (uint32_t k = 0; k < K; ++k) {
+      const QcRound* r = rc.rd[k];
+      ref[k] = QcRoundRef{r->owner(), r->bitmap(), r->count(), r->merged(), r->R(), (uint32_t)r->base, 0};
+    }
+    uint8_t* p = hr.data() + sizeof(QcRoundRef) * K;
+    memcpy(p, rc.g->gid.data(), 4 * n);
+    memcpy(p + 4 * n, sg.list.data(), 4 * sg.list.size());
+    memcpy(p + 4 * n + 4 * sg.list.size(), sg.seg.data(), 4 * sg.seg.size());
+  }
+  // as build_qc_locked: an error return drains the streams that copy from / into the host buffers
+  struct Drain {
+    hipStream_t s[3];
+    bool armed;
+    ~Drain() {
+      if (armed)
+        for (hipStream_t x : s)
+          if (x) (void)hipStreamSynchronize(x);
+    }
+  } drain{{c->stream, nullptr, nullptr}, true};
+  if (perm.empty()) {
+    HIPCHK(hipMemcpyAsync(d, sigs, n * 96, hipMemcpyHostToDevice, c->stream));
+    if (small) HIPCHK(hipMemcpyAsync(d + n * 96, hashes, n * 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d + n * 128, pks, n * 48, hipMemcpyHostToDevice, c->stream));
+  } else {
+    hb.resize(n * 176);
+    for (size_t j = 0; j < n; ++j) {
+      memcpy(&hb[96 * j], sigs + 96 * (size_t)perm[j], 96);
+      memcpy(&hb[n * 96 + 32 * j], hashes + 32 * (size_t)perm[j], 32);
+      memcpy(&hb[n * 128 + 48 * j], pks + 48 * (size_t)perm[j], 48);
+    }
+    HIPCHK(hipMemcpyAsync(d, hb.data(), n * 176, hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(hipMemcpyAsync(dorig, rc.g->orig.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(d + roff, hr.data(), rbytes, hipMemcpyHostToDevice, c->stream));
+  if (t) HIPCHK(hipMemcpyAsync(d + n * 180, tidx.data(), t * 4, hipMemcpyHostToDevice, c->stream));
+  int slot;
+  hipStream_t st;
+  if (small) {
+    // sigma of every staged vote into the side slab, beside the verify (as ovh_round_add)
+    constexpr uint32_t SL = 64 / VM_SIGCHK_W;
+    const Slab rsigma{c->rsig + (size_t)S_SIG * 12 * c->rsig_cap, c->rsig_cap};
+    soff.resize(n);
+    for (size_t j = 0; j < n; ++j) soff[j] = 96 * j;
+    HIPCHK(hipMemcpyAsync(d + zoff, soff.data(), 8 * n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(c->ev_x[2], c->stream));  // staged inputs
+    HIPCHK(hipStreamWaitEvent(c->xstream, c->ev_x[2], 0));
+    drain.s[2] = c->xstream;
+    k_vm_sigchk<<<(N + SL - 1) / SL, 64, LDS_SIGCHK, c->xstream>>>(N, c->vm_sigchk, c->vm_consts, d,
+                                                                   (const uint64_t*)(d + zoff), 0,
+                                                                   (int32_t*)(d + zoff + 8 * n), rsigma);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_x[3], c->xstream));
+    int ps[2];
+    CHK(verify_parts_locked(c, n, d, t, perm, hashes, dc, (uint32_t*)(d + pl.off), hent, ps));
+    slot = ps[1] >= 0 ? ps[1] : ps[0];
+    st = c->fs[slot];
+    if (ps[1] >= 0 && ps[0] >= 0) HIPCHK(hipStreamWaitEvent(st, c->ev_back[ps[0]], 0));
+  } else {
+    hp.resize(pl.bytes);
+    memcpy(hp.data(), pl.gid.data(), 4 * n);
+    memcpy(hp.data() + 4 * n, pl.ghash.data(), 32 * (size_t)pl.G);
+    memcpy(hp.data() + 4 * n + 32 * (size_t)pl.G, pl.head.data(), 4 * (size_t)pl.G);
+    if (!pl.pairs.empty()) memcpy(hp.data() + 4 * n + 36 * (size_t)pl.G, pl.pairs.data(), 4 * pl.pairs.size());
+    HIPCHK(hipMemcpyAsync(d + pl.off, hp.data(), hp.size(), hipMemcpyHostToDevice, c->stream));
+    const uint8_t* ex = d + pl.off;
+    const uint32_t* head = (const uint32_t*)(ex + 4 * n + 32 * (size_t)pl.G);
+    const SameMsgDev pd{pl.G, (const uint32_t*)ex, ex + 4 * n, head, head + pl.G, &pl.level_off};
+    CHK(take_slot(c, &slot));
+    CHK(verify_samemsg_locked(c, slot, n, d, t, dtidx, d + n * 128 + 48 * t, pd, dc));
+    st = c->fs[slot];
+  }
+  uint32_t* cur;
+  MsmArgs a = msm_args(c, slot, &cur);  // the MSM's bucket trees are done with: A holds the sums' tree
+  if (small) a.st = Slab{c->rsig, c->rsig_cap};
+  QcSel sel{};
+  sel.codes = dc;
+  sel.tidx = dtidx;
+  sel.orig = dorig;
+  sel.rank = tb.qc + tb.cap;
+  sel.gid = dgid;
+  sel.groups = K;
+  sel.bw = bw;
+  sel.taken = dtaken;
+  CHK(enqueue_qc_rounds(c, st, a, N, (uint32_t)t, sel, drefs, sg, dlist, dseg, gw, drows, rc.out_sigs ? d + ooff : nullptr,
+                        small ? c->ev_x[3] : nullptr));
+  HIPCHK(hipGetLastError());
+  drain.s[1] = st;
+  HIPCHK(hipMemcpyAsync(pc.data(), dc, 4 * n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(ptk.data(), dtaken, 4 * n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(rows.data(), drows, 4 * rows.size(), hipMemcpyDeviceToHost, st));
+  if (rc.out_sigs) HIPCHK(hipMemcpyAsync(sig96.data(), d + ooff, sig96.size(), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  drain.armed = false;
+  CHK(pool_failed(c));
+  for (size_t j = 0; j < n; ++j) {
+    const size_t i = perm.empty() ? j : perm[j];
+    codes[i] = pc[j];
+    if (taken) taken[i] = (uint8_t)ptk[j];
+  }
+  for (uint32_t k = 0; k < K; ++k) {
+    const uint32_t* row = &rows[(size_t)k * (1 + gw)];
+    rc.n_signed[k] = row[0];
+    if (rc.bitmaps) memcpy(rc.bitmaps + rc.bitmap_len * k, row + 1, rc.bitmap_len);
+    if (rc.out_sigs && row[0]) memcpy(rc.out_sigs + 96 * (size_t)k, &sig96[96 * (size_t)k], 96);
+  }
+  return 0;
+}
+
+int ovh_rounds_add(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint64_t* rounds, const uint8_t* pks, int32_t* codes,
+                   uint8_t* taken, uint32_t* slot, size_t max_rounds, uint32_t* n_rounds, uint64_t* round_ids,
+                   uint32_t* n_signed, uint8_t* out_sigs, uint8_t* bitmaps, size_t bitmap_len) {
+  if (!c || !sigs || !rounds || !pks || !codes || !n_rounds || !round_ids || !n_signed) return OVH_ERR_ARG;
+  if (n == 0 || n > OVH_ROUND_VOTES_MAX || max_rounds == 0) return OVH_ERR_ARG;
+  QcRoundGroups g;
+  qc_round_number(n, rounds, g);
+  if (g.K > max_rounds || g.K > OVH_ROUNDS_MAX) return OVH_ERR_ARG;
+  int r;
+  std::vector<uint8_t> hashes;
+  if (g.K == 1) {  // one vote, or every vote on one round: ovh_round_add itself
+    uint32_t cnt = 0;
+    r = ovh_round_add(c, g.ids[0], n, sigs, pks, codes, taken, &cnt, out_sigs, bitmaps, bitmap_len);
+    if (r) return r;
+    n_signed[0] = cnt;
+  } else {
+    hashes.resize(n * 32);  // the batch's and the verdict cache's per-vote form
+    ovh_ctx* s = c->sub.empty() ? c : c->sub[0];
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!s->tab.n || (bitmaps && bitmap_len != ((size_t)s->tab.n + 7) / 8)) return OVH_ERR_ARG;
+    QcRound* rd[OVH_ROUNDS_MAX];
+    for (uint32_t k = 0; k < g.K; ++k) {
+      rd[k] = round_find(s, g.ids[k]);
+      if (!rd[k] || rd[k]->base + g.cnt[k] > OVH_ROUND_VOTES_MAX) return OVH_ERR_ARG;
+    }
+    for (size_t i = 0; i < n; ++i) memcpy(&hashes[32 * i], rd[g.slot[i]]->hash, 32);
+    const QcRoundsCall rc{&g, rd, n_signed, out_sigs, bitmaps, bitmap_len};
+    r = rounds_add_locked(s, n, sigs, hashes.data(), pks, codes, taken, rc);
+    if (r == 0) {
+      for (uint32_t k = 0; k < g.K; ++k) rd[k]->base += g.cnt[k];  // by the round's own votes, not by n
+    } else {  // a device or RNG error: the words and R of every round of the call may be half updated
+      for (uint32_t k = 0; k < g.K; ++k) round_drop(s, g.ids[k]);
+      return r;
+    }
+  }
+  if (g.K > 1) cache_put(c, n, sigs, hashes.data(), pks, codes);
+  for (uint32_t k = 0; k < g.K; ++k) round_ids[k] = g.ids[k];
+  if (slot)
+    for (size_t i = 0; i < n; ++i) slot[i] = g.slot[i];
+  *n_rounds = g.K;
+  return 0;
 }
 
 int ovh_round_qc(ovh_ctx* c, uint64_t round, uint8_t out_sig[96], uint8_t* bitmap, size_t bitmap_len,

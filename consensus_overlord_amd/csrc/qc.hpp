@@ -12,6 +12,9 @@
 //   k_qc_compress the groups' sums to 96 bytes each (ovh_build_qcs)
 //   k_qc_rinit   a round's running sum to the identity (ovh_round_open)
 //   k_qc_merge   a round's running sum += one add's sum (ovh_round_add)
+//   k_qc_claim_r / k_qc_mark_r / k_qc_merge_seg / k_qc_rgather / k_qc_rcompress
+//                the same over the open rounds of one ovh_rounds_add call, through a table of
+//                round references (QcRoundRef)
 // The sum reads the sigma planes the same-message vote program left in the state slab (affine,
 // decompressed and subgroup-checked once); a vote that is not taken contributes the identity.
 // The kernels keep the MSM kernels' rules: no workgroup waits for another, the levels of a
@@ -197,4 +200,79 @@ __global__ __launch_bounds__(64) void k_qc_merge(const uint32_t* __restrict__ co
   MSM_VM_PROLOGUE(W);
   msm_pair_op<W>(padd, VM_PADD_NIN, slots, cst, lane, slice == 0, a, SRC_U, 0, SRC_A, 0, SRC_U, 0);
   if (threadIdx.x == 0) *merged = cnt;
+}
+
+// ovh_rounds_add: one pass over votes that belong to several open rounds.
+// Each round is an allocation of its own with a base of its own, so the call carries a device
+// table of K <= OVH_ROUNDS_MAX references, staged with the rest of the plan; QcSel::gid is the
+// vote's round number in the call (an index into the table, not the verify plan's hash group:
+// two rounds may be open on one hash), QcSel::orig its position among its round's votes in the
+// call. QcSel's owner / bitmap / count / groups / base are not read.
+struct QcRoundRef {
+  uint32_t* owner;
+  uint32_t* bitmap;
+  uint32_t* count;
+  uint32_t* merged;
+  uint32_t* R;    // the running sum, a one-entry slab
+  uint32_t base;  // the votes the round took in before this call
+  uint32_t pad;
+};
+
+__global__ __launch_bounds__(WG) void k_qc_claim_r(uint32_t t, QcSel s, const QcRoundRef* __restrict__ refs) {
+  const uint32_t j = blockIdx.x * WG + threadIdx.x;
+  if (j < t && s.codes[j] == 0) {
+    const QcRoundRef& r = refs[s.gid[j]];
+    atomicMin(&r.owner[(uint32_t)s.tidx[j]], r.base + s.orig[j]);
+  }
+}
+
+__global__ __launch_bounds__(WG) void k_qc_mark_r(uint32_t n, uint32_t t, QcSel s, const QcRoundRef* __restrict__ refs) {
+  const uint32_t j = blockIdx.x * WG + threadIdx.x;
+  bool tk = false;
+  if (j < t && s.codes[j] == 0) {
+    const QcRoundRef& r = refs[s.gid[j]];
+    const uint32_t e = (uint32_t)s.tidx[j];
+    tk = r.owner[e] == r.base + s.orig[j];
+    if (tk) {
+      const uint32_t k = s.rank[e];
+      atomicOr(&r.bitmap[k >> 5], 1u << (8 * ((k >> 3) & 3) + 7 - (k & 7)));
+      atomicAdd(r.count, 1u);
+    }
+  }
+  if (j < n) s.taken[j] = tk ? 1u : 0u;
+}
+
+// R_g <- R_g + (round g's sum of this call), workgroup g: k_qc_merge's body with R and the words
+// from the table and the source entry from the segment table (k_qc_chunk<true> / k_qc_upper<true>
+// leave round g's sum in A[32 seg[2 g]]). A round whose selection took nothing in this call has
+// count == merged and its R is not touched.
+__global__ __launch_bounds__(64) void k_qc_merge_seg(const QcRoundRef* __restrict__ refs, const uint32_t* __restrict__ seg,
+                                                     VmDev padd, uint32_t stride_w, const uint32_t* __restrict__ cst_g,
+                                                     MsmArgs a) {
+  constexpr uint32_t W = VM_PADD_W;
+  const QcRoundRef r = refs[blockIdx.x];
+  const uint32_t cnt = *r.count;
+  if (cnt == *r.merged) return;  // uniform; merged is written behind the barriers below
+  a.U = Slab{r.R, 1};
+  const uint32_t src = seg[2 * blockIdx.x] << (MSM_CH_LV - 1);
+  MSM_VM_PROLOGUE(W);
+  msm_pair_op<W>(padd, VM_PADD_NIN, slots, cst, lane, slice == 0, a, SRC_U, 0, SRC_A, src, SRC_U, 0);
+  if (threadIdx.x == 0) *r.merged = cnt;
+}
+
+// Round g's count and bitmap words into the call's output rows (row g: count | bw bitmap words;
+// bw 0: the count alone), so the host reads K rounds with one copy.
+__global__ __launch_bounds__(64) void k_qc_rgather(const QcRoundRef* __restrict__ refs, uint32_t bw, uint32_t* out) {
+  const QcRoundRef& r = refs[blockIdx.x];
+  uint32_t* row = out + (size_t)blockIdx.x * (1 + bw);
+  if (threadIdx.x == 0) row[0] = *r.count;
+  for (uint32_t w = threadIdx.x; w < bw; w += 64) row[1 + w] = r.bitmap[w];
+}
+
+// Round g's R -> 96 bytes at out + 96 g (one lane, as k_qc_compress); an empty round is skipped
+__global__ __launch_bounds__(64) void k_qc_rcompress(const QcRoundRef* __restrict__ refs, uint8_t* out) {
+  if (threadIdx.x) return;
+  const QcRoundRef& r = refs[blockIdx.x];
+  if (*r.count == 0) return;
+  g2p_compress(Slab{r.R, 1}, 0, out + 96 * (size_t)blockIdx.x);
 }

@@ -34,7 +34,10 @@ of each signed hash, in arrival order, to that hash's device round (`ConsensusCr
 adds the taken signatures to the round's running sum) in place of `prefetch`; chokes and every
 other encoding go to `prefetch` as before. `VoteIngress.qc(hash)` reads the round's QC with no
 second pass over the quorum. Rounds are opened on first use; when ROUNDS_MAX are open the one
-opened first is closed.
+opened first is closed. A flush whose votes sign two or more hashes (the block hash and the nil
+vote, precommits beside late prevotes) is one device pass over all its rounds
+(`ConsensusCrypto.add_rounds` -> `ovh_rounds_add`), not one pass per hash; `stats["round_passes"]`
+counts the passes.
 
 Wire layouts [dep: overlord 0.4 types + rlp 0.5, not vendored; named assumption 7 in DESIGN.md]:
   SignedVote   = rlp([signature bytes, Vote, voter bytes])
@@ -171,7 +174,9 @@ class VoteIngress:
         self.use_rounds = bool(rounds) and hasattr(crypto, "open_round")
         self.rounds: "OrderedDict[bytes, object]" = OrderedDict()   # signed hash -> Round, oldest first
         if self.use_rounds:
-            self.stats.update({"round_adds": 0, "round_votes": 0})
+            # round_adds / round_votes: one per (round, flush) and its votes; round_passes: the
+            # device passes they took (one per flush over several hashes with add_rounds)
+            self.stats.update({"round_adds": 0, "round_votes": 0, "round_passes": 0})
 
     def _limit(self) -> int:
         if self.batch_size:
@@ -256,17 +261,26 @@ class VoteIngress:
         for p in items:
             self._send(p.kind, p.msg)
 
-    def _round(self, h: bytes):
+    def _round(self, h: bytes, keep=(), later=()):
         r = self.rounds.get(h)
         if r is None:
             if len(self.rounds) >= ROUNDS_MAX:
-                self.rounds.popitem(last=False)[1].close()   # the round opened first
+                # the round opened first -- among those the flush does not need at all, else among
+                # those the call being prepared does not need
+                old = next((k for k in self.rounds if k not in keep and k not in later), None)
+                if old is None:
+                    old = next(k for k in self.rounds if k not in keep)
+                self.rounds.pop(old).close()
             r = self.rounds[h] = self.crypto.open_round(h)
         return r
 
     def _add_to_rounds(self, items, hs, fixed) -> List[int]:
         """The fixed-size SignedVotes among `fixed`, grouped by signed hash in arrival order, go to
-        their rounds; returns what is left for prefetch."""
+        their rounds; returns what is left for prefetch. A flush on one hash is one Round.add. A
+        flush over two or more hashes is one device pass (`crypto.add_rounds`, when the crypto has
+        it) over all of them in arrival order, cut into calls of at most ROUNDS_MAX rounds; every
+        round of a call is resolved before the call, and opening one never closes another that the
+        same call needs. Without add_rounds: one Round.add per hash, as before."""
         groups: "OrderedDict[bytes, List[int]]" = OrderedDict()
         rest = []
         for k in fixed:
@@ -274,8 +288,25 @@ class VoteIngress:
                 groups.setdefault(hs[k], []).append(k)
             else:
                 rest.append(k)
+        if len(groups) >= 2 and hasattr(self.crypto, "add_rounds"):
+            order = list(groups)
+            for lo in range(0, len(order), ROUNDS_MAX):
+                part = order[lo:lo + ROUNDS_MAX]
+                rounds = {h: self._round(h, keep=part, later=order[lo:]) for h in part}
+                if len(part) == 1:
+                    ks = groups[part[0]]
+                    rounds[part[0]].add([items[k].signature for k in ks], [items[k].voter for k in ks])
+                else:
+                    ks = sorted(k for h in part for k in groups[h])
+                    self.crypto.add_rounds([rounds[hs[k]] for k in ks], [items[k].signature for k in ks],
+                                           [items[k].voter for k in ks])
+                self.stats["round_passes"] += 1
+                self.stats["round_adds"] += len(part)
+                self.stats["round_votes"] += len(ks)
+            return rest
         for h, ks in groups.items():
             self._round(h).add([items[k].signature for k in ks], [items[k].voter for k in ks])
+            self.stats["round_passes"] += 1
             self.stats["round_adds"] += 1
             self.stats["round_votes"] += len(ks)
         return rest

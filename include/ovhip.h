@@ -372,6 +372,47 @@ int ovh_round_qc(ovh_ctx* ctx, uint64_t round, uint8_t out_sig[96], uint8_t* bit
                  uint32_t* n_signed);
 int ovh_round_close(ovh_ctx* ctx, uint64_t round);
 
+/* A flush's votes added to several open rounds in one device pass: the votes of one flush split
+ * between the block hash and the nil vote, with late votes of another round beside them, and one
+ * ovh_round_add per hash pays the fixed latency of a device pass each time. rounds[i] is the id
+ * of the open round that vote i is for; that round's hash is the hash the vote is verified under.
+ * One verify of all n votes, one final exponentiation, then selection, sum and merge per round,
+ * behind one host synchronisation. Host buffers, synchronous, thread-safe; a multi-device context
+ * runs the call on its first device.
+ * The defining property: take any call and any round r named in it. The codes and taken of r's
+ * votes, and r's n_signed, bitmap and 96 bytes after the call, equal what ovh_round_add(r, the
+ * sub-list of r's votes in the caller's order) would have written in its place. Hence any
+ * interleaving of ovh_rounds_add and ovh_round_add calls leaves every round equal, byte for byte,
+ * to ovh_build_qc over the concatenation of that round's votes. A voter with valid votes in two
+ * rounds is taken in both: each QC stands alone, as in ovh_build_qcs. Two rounds opened on the
+ * same hash stay two rounds.
+ *   numbering     the distinct ids are numbered by first appearance in the caller's order: slot[i]
+ *                 (may be NULL) is vote i's number, round_ids[k] the id of number k, *n_rounds
+ *                 their count K.
+ *   codes, taken  per vote, as ovh_round_add's. The verdicts enter the verdict cache.
+ *   n_signed[k]   the cumulative count of round k.
+ *   bitmaps[k]    (may be NULL; else bitmap_len == ceil(table size / 8) bytes each, checked only
+ *                 then) the cumulative bitmap of round k, ovh_build_qc's layout.
+ *   out_sigs[k]   (may be NULL; 96 B each) the compressed cumulative sum of round k, written only
+ *                 when n_signed[k] > 0. With NULL no compression runs.
+ * A round's budget (OVH_ROUND_VOTES_MAX) counts only its own votes.
+ * Routes: n == 1, or every vote on one round, is ovh_round_add itself. Else 2 .. OVH_SMALL_MAX
+ * votes are verified as ovh_prefetch verifies those votes with their per-vote hashes (the
+ * small-batch path, on the message cache's H where ovh_round_open primed it), and more votes (or
+ * OVH_SAMEMSG=2) on the same-message route over the per-vote hashes, as ovh_build_qcs.
+ * Returns 0 whenever the outputs were written, also when nothing was taken. OVH_ERR_ARG for a NULL
+ * required pointer, n == 0, no validator table, any id that is unknown or closed, more distinct
+ * ids than max_rounds (or than OVH_ROUNDS_MAX), a round that would pass OVH_ROUND_VOTES_MAX, or a
+ * wrong bitmap_len: all decided on the host before any device work. A refused call changes
+ * nothing: no round's budget moves and no device word is touched. A device or RNG error closes
+ * every round named in the call. */
+int ovh_rounds_add(ovh_ctx* ctx, size_t n, const uint8_t* sigs /* n x 96 */, const uint64_t* rounds /* n */,
+                   const uint8_t* pks /* n x 48 */, int32_t* codes /* n */, uint8_t* taken /* n, may be NULL */,
+                   uint32_t* slot /* n, may be NULL */, size_t max_rounds, uint32_t* n_rounds,
+                   uint64_t* round_ids /* max_rounds */, uint32_t* n_signed /* max_rounds */,
+                   uint8_t* out_sigs /* max_rounds x 96, may be NULL */,
+                   uint8_t* bitmaps /* max_rounds x bitmap_len, may be NULL */, size_t bitmap_len);
+
 /* TESTS ONLY (context created with OVH_FLAG_TEST_RLC, else OVH_ERR_ARG): vote i of every
  * following batch gets the coefficient SplitMix64(seed, index_base + i). Predictable
  * coefficients let an adversary cancel invalid signatures inside the combined check

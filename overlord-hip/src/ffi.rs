@@ -75,6 +75,7 @@ extern "C" {
     pub fn ovh_build_qcs(ctx: *mut OvhCtx, n: usize, sigs: *const u8, hashes: *const u8, pks: *const u8, codes: *mut i32, taken: *mut u8, group: *mut u32, max_groups: usize, n_groups: *mut u32, group_hashes: *mut u8, out_sigs: *mut u8, bitmaps: *mut u8, bitmap_len: usize, n_signed: *mut u32) -> i32;
     pub fn ovh_round_open(ctx: *mut OvhCtx, hash: *const u8, hash_len: usize, round: *mut u64) -> i32;
     pub fn ovh_round_add(ctx: *mut OvhCtx, round: u64, n: usize, sigs: *const u8, pks: *const u8, codes: *mut i32, taken: *mut u8, n_signed: *mut u32, out_sig: *mut u8, bitmap: *mut u8, bitmap_len: usize) -> i32;
+    pub fn ovh_rounds_add(ctx: *mut OvhCtx, n: usize, sigs: *const u8, rounds: *const u64, pks: *const u8, codes: *mut i32, taken: *mut u8, slot: *mut u32, max_rounds: usize, n_rounds: *mut u32, round_ids: *mut u64, n_signed: *mut u32, out_sigs: *mut u8, bitmaps: *mut u8, bitmap_len: usize) -> i32;
     pub fn ovh_round_qc(ctx: *mut OvhCtx, round: u64, out_sig: *mut u8, bitmap: *mut u8, bitmap_len: usize, n_signed: *mut u32) -> i32;
     pub fn ovh_round_close(ctx: *mut OvhCtx, round: u64) -> i32;
     pub fn ovh_set_test_rlc(ctx: *mut OvhCtx, seed: u64, index_base: u64) -> i32;

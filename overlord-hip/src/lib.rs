@@ -380,7 +380,48 @@ impl HipCrypto {
         check(unsafe { ffi::ovh_round_open(self.raw(), hash.as_ptr(), hash.len(), &mut id) })?;
         Ok(Round { ctx: self.ctx.clone(), id, bitmap_len: (self.pubkeys.blocking_read().len() + 7) / 8 })
     }
+
+    /// A flush's votes added to several open rounds in one device pass (`ovh_rounds_add`):
+    /// `rounds[i]` is the round vote `i` is for, and the vote is verified under that round's hash.
+    /// Every round ends as if `Round::add` had been called with the sub-list of its votes.
+    /// Returns the per-vote codes and taken flags, then per distinct round, in order of first
+    /// appearance: (round id, cumulative count, signature when `want_qc` and the count is not 0,
+    /// bitmap when `want_qc`). `CryptoErr(OVH_ERR_ARG)` changes nothing; a device error closes the
+    /// rounds of the call. Blocking.
+    pub fn rounds_add(&self, rounds: &[&Round], sigs: &[[u8; 96]], voters: &[[u8; 48]], want_qc: bool) -> Result<RoundsAdd, Box<dyn Error + Send>> {
+        if sigs.len() != voters.len() || sigs.len() != rounds.len() {
+            return Err(to_err(ffi::OVH_ERR_LEN_MISMATCH));
+        }
+        let ids: Vec<u64> = rounds.iter().map(|r| r.id).collect();
+        let mr = ffi::OVH_ROUNDS_MAX;
+        let bl = (self.pubkeys.blocking_read().len() + 7) / 8;
+        let mut codes = vec![0i32; sigs.len()];
+        let mut taken = vec![0u8; sigs.len()];
+        let mut n_rounds = 0u32;
+        let mut round_ids = vec![0u64; mr];
+        let mut n_signed = vec![0u32; mr];
+        let mut out_sigs = vec![[0u8; 96]; mr];
+        let mut bitmaps = vec![0u8; mr * bl];
+        let (po, pb) = if want_qc { (out_sigs.as_mut_ptr() as *mut u8, bitmaps.as_mut_ptr()) } else { (std::ptr::null_mut(), std::ptr::null_mut()) };
+        check(unsafe {
+            ffi::ovh_rounds_add(self.raw(), sigs.len(), sigs.as_ptr() as *const u8, ids.as_ptr(), voters.as_ptr() as *const u8,
+                                codes.as_mut_ptr(), taken.as_mut_ptr(), std::ptr::null_mut(), mr, &mut n_rounds,
+                                round_ids.as_mut_ptr(), n_signed.as_mut_ptr(), po, pb, bl)
+        })?;
+        let per_round = (0..n_rounds as usize)
+            .map(|k| {
+                let sig = if want_qc && n_signed[k] > 0 { Some(Bytes::copy_from_slice(&out_sigs[k])) } else { None };
+                let bm = if want_qc { Some(Bytes::copy_from_slice(&bitmaps[k * bl..(k + 1) * bl])) } else { None };
+                (round_ids[k], n_signed[k], sig, bm)
+            })
+            .collect();
+        Ok((codes, taken, per_round))
+    }
 }
+
+/// What `HipCrypto::rounds_add` returns: per-vote codes and taken flags, then per distinct round
+/// (id, cumulative count, signature, bitmap).
+pub type RoundsAdd = (Vec<i32>, Vec<u8>, Vec<(u64, u32, Option<Bytes>, Option<Bytes>)>);
 
 /// One open round of a `HipCrypto` (`ovh_round_open` .. `ovh_round_close`). For any cut of a vote
 /// list into consecutive `add`s the codes, the taken flags, the count, the bitmap and the
@@ -397,6 +438,11 @@ pub struct Round {
 pub type RoundAdd = (Vec<i32>, Vec<u8>, u32, Option<(Option<Bytes>, Bytes)>);
 
 impl Round {
+    /// The id `ovh_round_open` gave the round.
+    pub fn id(&self) -> u64 {
+        self.id
+    }
+
     /// Verify `sigs.len()` more votes on the round's hash, select, and add the taken signatures
     /// to the round's sum, in one device pass over these votes only (`ovh_round_add`). Pass
     /// `want_qc` when this add is expected to cross the threshold: the compression then rides

@@ -10,7 +10,9 @@ hash seen before (message cache warm) in every arm:
              opened and the first N - k votes were added before the timer starts
 for k = 1 and k = 8. One process; a repetition runs the three arms in turn; repetition 0 warms every
 path up and is not recorded. The three arms must build the same signature. Prints one JSON line
-per (N, k) with the medians, minima and maxima in ms.   python tools/round_probe.py [--reps 25]"""
+per (N, k) with the medians, minima and maxima in ms.   python tools/round_probe.py [--reps 25]
+With --split: a last flush split over several hashes, one ovh_round_add per hash against one
+ovh_rounds_add (split_main)."""
 import argparse
 import ctypes
 import hashlib
@@ -34,11 +36,132 @@ def _ms(fn):
     return (time.perf_counter() - t) * 1e3
 
 
+SPLITS = ((6, 2), (4, 3, 1), (34, 33))   # the last flush's votes per hash
+
+
+def split_main(args):
+    """--split: what a last flush that is split over several hashes costs, per validator table and
+    per shape of SPLITS, every round filled up to its last votes before the timer starts, QC bytes
+    and bitmaps requested:
+      per_round   one ovh_round_add per hash in sequence (only calls that exist since section 3.8:
+                  the same script gives the baseline on a library without ovh_rounds_add)
+      rounds_add  one ovh_rounds_add over the flush in arrival order (hashes interleaved)
+    A repetition opens fresh rounds for each arm; repetition 0 is not recorded; both arms must give
+    the same bytes, bitmap and count per round. One JSON line per (N, shape)."""
+    import torch
+    import bench
+    from consensus_overlord_amd import device as dev
+    from consensus_overlord_amd.crypto import Context
+    ctx = Context(0)
+    lib = ctx.lib
+    vp = ctypes.c_void_p
+    p = lambda a: a.ctypes.data_as(vp)   # noqa: E731
+    have = hasattr(lib, "ovh_rounds_add")
+    for n in TABLES:
+        sks_h, _ = bench.synth_inputs(lib, 0, n)
+        sks = torch.from_numpy(sks_h).cuda()
+        pk = dev.sk_to_pk_batch(ctx, sks).cpu().numpy()
+        assert lib.ovh_set_validators(ctx.ptr, pk.tobytes(), n) == 0
+        bl = (n + 7) // 8
+        for shape in SPLITS:
+            # hash g has the votes of size[g] validators of its own (the whole table when the flush
+            # is the whole round), the first size[g] - shape[g] of them added before the timer starts
+            G = len(shape)
+            size = [max(m, n // G) for m in shape]
+            off = [sum(size[:g]) for g in range(G)]
+            assert sum(size) <= n
+            hashes = [hashlib.sha256(b"round probe split %d %d %d" % (n, G, g)).digest() for g in range(G)]
+            sg = [dev.sign_batch(ctx, sks[off[g]:off[g] + size[g]],
+                                 torch.from_numpy(np.tile(np.frombuffer(hashes[g], dtype=np.uint8), (size[g], 1))).cuda())
+                  .cpu().numpy() for g in range(G)]
+            pkg = [pk[off[g]:off[g] + size[g]] for g in range(G)]
+            # the flush in arrival order: the hashes' last votes, round-robin
+            flush = []
+            left = list(shape)
+            while any(left):
+                for g in range(G):
+                    if left[g]:
+                        flush.append((g, size[g] - left[g]))
+                        left[g] -= 1
+            k = len(flush)
+            fl_s = b"".join(sg[g][i].tobytes() for g, i in flush)
+            fl_p = b"".join(pkg[g][i].tobytes() for g, i in flush)
+
+            def fill():
+                """fresh rounds with everything but the flush added"""
+                ids = []
+                codes, cnt = np.zeros(max(size), dtype=np.int32), ctypes.c_uint32(0)
+                for g in range(G):
+                    rid = ctypes.c_uint64(0)
+                    assert lib.ovh_round_open(ctx.ptr, hashes[g], 32, ctypes.byref(rid)) == 0
+                    lo = size[g] - shape[g]
+                    if lo:
+                        assert lib.ovh_round_add(ctx.ptr, rid.value, lo, sg[g][:lo].tobytes(), pkg[g][:lo].tobytes(),
+                                                 p(codes), None, ctypes.byref(cnt), None, None, 0) == 0 and cnt.value == lo
+                    ids.append(rid.value)
+                return ids
+
+            def close(ids):
+                for rid in ids:
+                    assert lib.ovh_round_close(ctx.ptr, rid) == 0
+
+            def per_round():
+                ids = fill()
+                outs = [(ctypes.create_string_buffer(96), ctypes.create_string_buffer(bl), ctypes.c_uint32(0)) for _ in ids]
+                codes = np.zeros(k, dtype=np.int32)
+
+                def last():
+                    for g, rid in enumerate(ids):
+                        lo = size[g] - shape[g]
+                        assert lib.ovh_round_add(ctx.ptr, rid, shape[g], sg[g][lo:].tobytes(), pkg[g][lo:].tobytes(),
+                                                 p(codes), None, ctypes.byref(outs[g][2]), outs[g][0], outs[g][1], bl) == 0
+                ms = _ms(last)
+                close(ids)
+                return ms, [(o.raw, b.raw, c.value) for o, b, c in outs]
+
+            def rounds_add():
+                ids = fill()
+                idv = np.array([ids[g] for g, _ in flush], dtype=np.uint64)
+                codes = np.zeros(k, dtype=np.int32)
+                rid, cnt = np.zeros(16, dtype=np.uint64), np.zeros(16, dtype=np.uint32)
+                out, bm = np.zeros((16, 96), dtype=np.uint8), np.zeros((16, bl), dtype=np.uint8)
+                nr = ctypes.c_uint32(0)
+
+                def last():
+                    assert lib.ovh_rounds_add(ctx.ptr, k, fl_s, p(idv), fl_p, p(codes), None, None, 16, ctypes.byref(nr),
+                                              p(rid), p(cnt), p(out), p(bm), bl) == 0
+                ms = _ms(last)
+                assert nr.value == G and rid[:G].tolist() == ids and not codes.any()
+                close(ids)
+                return ms, [(out[g].tobytes(), bm[g].tobytes(), int(cnt[g])) for g in range(G)]
+
+            t = {"per_round_ms": [], "rounds_add_ms": []}
+            for rep in range(args.reps + 1):
+                a, qa = per_round()
+                assert [q[2] for q in qa] == size
+                if have:
+                    b, qb = rounds_add()
+                    assert qa == qb, "the two arms disagree"
+                if rep:
+                    t["per_round_ms"].append(a)
+                    if have:
+                        t["rounds_add_ms"].append(b)
+            row = {"validators": n, "split": list(shape), "reps": args.reps}
+            for name, v in t.items():
+                if v:
+                    row[name] = {"median": round(float(np.median(v)), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+            print(json.dumps(row), flush=True)
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=25)
+    ap.add_argument("--split", action="store_true", help="a last flush split over several hashes (section 3.9)")
     args = ap.parse_args()
     assert args.reps >= 20, "medians of at least 20 repetitions"
+    if args.split:
+        return split_main(args)
     import torch
     import bench
     from consensus_overlord_amd import device as dev
