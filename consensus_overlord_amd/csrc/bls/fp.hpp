@@ -168,6 +168,52 @@ OVH_HD void fp_mul(Fp& r, const Fp& a, const Fp& b) {
 #endif
 }
 
+// The wide Montgomery product r = a * b * 2^-392 mod p for a, b < 4p, with r <= p + floor(a b /
+// 2^392) < 1.0064 p and NO conditional subtraction (392 = 14 x 28, the radix the device product
+// works in; bls/fp_mul28.hpp). The Fp-VM runs its radix-392 programs on it (fpvm.hpp). Device:
+// fp_mul28w_gfx950. Host: the CIOS loop above without its subtraction (T < 2.63 p in 12 limbs),
+// then one more Montgomery step of 8 bits -- equal to the device's value modulo p and under the
+// same bound, not limb for limb.
+OVH_HD void fp_mul_wide(Fp& r, const Fp& a, const Fp& b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#if defined(OVH_FPMUL28_2ACC) || defined(OVH_FPMUL_2ACC)
+#error "the wide product (radix 2^392) has the one-accumulator 14 x 28 form only"
+#endif
+  fp_mul28w_gfx950(r.v, a.v, b.v);
+#else
+  OVH_COUNT_MUL();
+  uint32_t t[13];
+#pragma unroll
+  for (int j = 0; j < 13; ++j) t[j] = 0;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    const uint32_t bi = b.v[i];
+    uint64_t c = (uint64_t)a.v[0] * bi + t[0];
+    t[0] = (uint32_t)c;
+    const uint32_t m = t[0] * P_INV32;
+    uint64_t c2 = (uint64_t)m * P_LIMBS[0] + t[0];
+#pragma unroll
+    for (int j = 1; j < 12; ++j) {
+      c = (uint64_t)a.v[j] * bi + t[j] + (c >> 32);
+      c2 = (uint64_t)m * P_LIMBS[j] + (uint32_t)c + (c2 >> 32);
+      t[j - 1] = (uint32_t)c2;
+    }
+    t[11] = (uint32_t)(c >> 32) + (uint32_t)(c2 >> 32);
+  }
+  // (T + m8 p) / 2^8, m8 = -T / p mod 2^8: T + m8 p < 259 p needs the 13th limb
+  const uint32_t m8 = (t[0] * P_INV32) & 0xFFu;
+  uint64_t cy = 0;
+#pragma unroll
+  for (int j = 0; j < 12; ++j) {
+    cy = (uint64_t)m8 * P_LIMBS[j] + t[j] + (cy >> 32);
+    t[j] = (uint32_t)cy;
+  }
+  t[12] = (uint32_t)(cy >> 32);
+#pragma unroll
+  for (int j = 0; j < 12; ++j) r.v[j] = (t[j] >> 8) | (t[j + 1] << 24);
+#endif
+}
+
 OVH_HD void fp_sqr(Fp& r, const Fp& a) { fp_mul(r, a, a); }
 
 // r = a * small (small < 2^16), via repeated doubling-free Montgomery-free path:

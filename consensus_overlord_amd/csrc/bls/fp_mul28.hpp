@@ -7,6 +7,11 @@
 // tests/test_gpu_fp_bounds.py checks this form, the two asm forms of fp_mul28_gfx950.hpp and
 // fp_mul_gfx950 on the device against exact integers at the limb and range edges
 // (tests/fp_cases.py); tools/ubench/fp_mul28.hip times it against fp_mul_gfx950.
+//
+// The wide form (fp_mul28w_gfx950, generated beside the others) keeps R = 2^392: neither operand
+// is shifted, r = a b 2^-392 mod p, and for a, b < 4p the column sum T = (a b + m p) / 2^392 is
+// below 16 (p / 2^392) p + p < 1.0064 p -- already inside the Fp-VM's [0, 2p) slot range, so the
+// join has no conditional subtraction. The vote pool's programs run on it (fpvm.hpp, radix 392).
 #pragma once
 #include <stdint.h>
 
@@ -39,6 +44,27 @@ __device__ __forceinline__ void split28(uint32_t* x, const uint32_t* a) {
       if (s > 4 && w + 1 < 12) v |= a[w + 1] << (32 - s);
     }
     x[k] = v & M28;
+  }
+}
+
+// 14 x 28 -> 12 x 32 (no reduction)
+__device__ __forceinline__ void join28(uint32_t* u, const uint32_t* t) {
+#if defined(OVH_UBENCH_NOSPLIT)
+#pragma unroll
+  for (int j = 0; j < 12; ++j) u[j] = t[j];
+  return;
+#endif
+  // 32 j = 28 k + s with s in {0, 4, .., 24}: limb j is t[k] >> s | t[k + 1] << (28 - s), one shift
+  // and one v_lshl_or_b32 (written out: left to itself the compiler at times takes three
+  // instructions per limb, a third more for the whole join)
+#pragma unroll
+  for (int j = 0; j < 12; ++j) {
+    const int k = (32 * j) / 28, s = (32 * j) % 28;
+    static_assert(28 % 4 == 0, "s <= 24: no third limb");
+    const uint32_t lo = s ? t[k] >> s : t[k];
+    uint32_t v;
+    asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(v) : "v"(t[k + 1]), "n"(28 - s), "v"(lo));
+    u[j] = v;
   }
 }
 

@@ -15,6 +15,18 @@
 // k <= 15 < 120p) and reduce once by a float estimate of the quotient to [0, 2p). Only the ops
 // whose result depends on the canonical value (sgn0, lex, the equality test, `st` outputs,
 // inversion) canonicalise: a product by the plain 1 of a value below 4p is at most p.
+//
+// Radix. A program's Montgomery radix travels with it: 2^384 (every program but the vote pool's),
+// or 2^392 = 2^(14 x 28), the radix the device product works in (bls/fp_mul28.hpp), for `vote`
+// and `vote_t` (tools/fpvm/progs.py; VM_<PROG>_RADIX). A radix-392 ("wide") product takes both
+// operands as they are and needs no conditional subtraction: T = (a b + m p) / 2^392 <= a b /
+// 2^392 + p < 16 (p / 2^392) p + p = 1.0064 p for a, b < 4p, inside the [0, 2p) slot range. The
+// wide product of x < 4p by the plain 1 is at most p, and equals p exactly for x in {p, 2p, 3p},
+// so the flag ops (sgn0, lex, eq) test for that one non-canonical value, in flag phases only. Slots,
+// lin, sel, selb, `st` and canon do not depend on the radix (sums reduce modulo 2^384 limbs).
+// Every product op of a wide program carries W_WIDE (w3 bit 25, tools/fpvm/sched.py), the same
+// in every lane of a product phase; exec's RADIX parameter fixes the radix at compile time (384:
+// the code of before; 392: no branch, no subtraction) or, 0, reads that bit per phase.
 // tests/test_fp_bounds_host.py (host build) and tests/test_gpu_fp_bounds.py (device) run each of
 // these clauses at its bounds against exact integers (tests/fp_cases.py).
 #pragma once
@@ -281,6 +293,15 @@ VM_FN void pre_add2(Fp& x, const Fp& A, const Fp& B, Fp& y, const Fp& C, const F
   }
 }
 
+// w3 bit 25 of a product op: the program's radix is 2^392 (tools/fpvm/sched.py WIDE)
+constexpr uint32_t W_WIDE = 1u << 25;
+// The radix exec / run bind when a caller names none: 0 decides per phase from W_WIDE (tests,
+// probes, microbenchmarks: any program); the library fixes 384 (ovhip.hip) and names 392 where it
+// binds the pool's vote programs.
+#ifndef OVH_VM_RADIX
+#define OVH_VM_RADIX 0
+#endif
+
 // phase header bits (w0 bits 22..31, tools/fpvm/sched.py H_*)
 constexpr uint32_t H_MUL = 1u << 22, H_MULNEG = 1u << 23, H_FLAG = 1u << 24, H_LIN = 1u << 25,
                    H_LINNEG = 1u << 26, H_ACC = 1u << 27, H_RARE = 1u << 28, H_SELB = 1u << 29,
@@ -376,7 +397,9 @@ VM_FN int coef5(uint32_t w, int lo) { return ((int)(w << (27 - lo))) >> 27; }
 // INV: whether the interpreter carries the inversion (the divsteps loop and its products, about a
 // third of exec's code). Only programs with an `inv` op need it (VM_<PROG>_HAS_INV, vm_progs.inc);
 // without it an `inv` op stores its operand unchanged, so a kernel static_asserts on its program.
-template <bool INV = true>
+// RADIX: 384, 392, or 0 = per phase from W_WIDE of the wave's first lane (a product phase's lane 0
+// is a product op: sched.encode asserts it for wide programs).
+template <bool INV = true, int RADIX = OVH_VM_RADIX>
 VM_FN void exec(const uint4 in, bool active, uint32_t* __restrict__ slots, const uint32_t* __restrict__ cst,
                 uint64_t scalar, const Out& out) {
   // the phase header (bits 22.. of w0, equal in every lane; tools/fpvm/sched.py phase_bits) names
@@ -412,13 +435,31 @@ VM_FN void exec(const uint4 in, bool active, uint32_t* __restrict__ slots, const
     const bool is_mul = op == OP_MULS || op == OP_SGN0 || op == OP_LEX || op == OP_EQ;
     Fp x, y, m;
     pre_add2(x, A, B, y, C, D, sign_mask(in.w, 19) != 0, (hdr & H_MULNEG) != 0);
-    fp_mul(m, x, y);
+    static_assert(RADIX == 0 || RADIX == 384 || RADIX == 392, "Fp-VM radix: 2^384, 2^392 or per phase (0)");
+    const bool wide = RADIX == 392 || (RADIX == 0 && (uniform(in.w) & W_WIDE) != 0);
+    if constexpr (RADIX == 384) {
+      fp_mul(m, x, y);
+    } else if constexpr (RADIX == 392) {
+      fp_mul_wide(m, x, y);
+    } else {
+      if (wide) fp_mul_wide(m, x, y);
+      else fp_mul(m, x, y);
+    }
     if (hdr & H_FLAG) {  // m is canonical here: the product of a value below 4p and the plain 1
       const bool flag = is_mul && op != OP_MULS;
       uint32_t f = 0;
       if (op == OP_SGN0) f = m.v[0] & 1u;
       if (op == OP_LEX) f = limbs_gt(m.v, HALF_P) ? 1u : 0u;
       if (op == OP_EQ) f = fp_is_zero(m) ? 1u : 0u;
+      // (a wide product by the plain 1 is at most p, and p itself for x = p, 2p, 3p: the one
+      // non-canonical value, whose flags are those of 0. An equality test, no borrow chain, and
+      // in flag phases only)
+      if (wide) {
+        uint32_t d = 0;
+#pragma unroll
+        for (int j = 0; j < 12; ++j) d |= m.v[j] ^ P_LIMBS[j];
+        if (d == 0) f = op == OP_EQ ? 1u : 0u;
+      }
 #pragma unroll
       for (int j = 0; j < 12; ++j) m.v[j] = flag ? (j == 0 ? f : 0u) : m.v[j];
     }
@@ -508,7 +549,7 @@ __device__ __forceinline__ void side_spill(uint32_t sw, uint32_t* __restrict__ s
 #define OVH_VM_UNROLL 1
 #endif
 
-template <bool SIDE = false, bool INV = true, int UNROLL = OVH_VM_UNROLL>
+template <bool SIDE = false, bool INV = true, int UNROLL = OVH_VM_UNROLL, int RADIX = OVH_VM_RADIX>
 __device__ __forceinline__ void run(const uint4* __restrict__ code, uint32_t nphases, uint32_t W, uint32_t lane,
                                     bool active, uint32_t* __restrict__ slots, const uint32_t* __restrict__ cst,
                                     uint64_t scalar, const Out& out, uint64_t* __restrict__ trace = nullptr,
@@ -547,7 +588,7 @@ __device__ __forceinline__ void run(const uint4* __restrict__ code, uint32_t nph
       }
       q2 = code[(size_t)(ph + QD) * W + lane];
       s2 = active ? side[(size_t)(ph + 2) * W + lane] : 0u;
-      exec<INV>(q, active, slots, cst, scalar, out);
+      exec<INV, RADIX>(q, active, slots, cst, scalar, out);
       // this phase's spill reads its slot before the fill lands: a fill may take the slot of a
       // value whose last read is this spill
       side_spill(s, slots, scr);
@@ -589,7 +630,7 @@ __device__ __forceinline__ void run(const uint4* __restrict__ code, uint32_t nph
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), as above
   auto step = [&](const uint4& q, uint4& q2, const uint32_t ph) __attribute__((always_inline)) {
     q2 = code[(size_t)(ph + (UNROLL == 3 ? 2 : 1)) * W + lane];
-    exec<INV>(q, active, slots, cst, scalar, out);
+    exec<INV, RADIX>(q, active, slots, cst, scalar, out);
     if (trace && ph < nphases) {
       __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       if (threadIdx.x == 0) trace[ph + 1] = wall_clock64();

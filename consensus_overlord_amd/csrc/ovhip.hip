@@ -44,7 +44,11 @@
 
 #include "../../include/ovhip.h"
 #include "bls/verify.hpp"
+// every kernel here binds the radix-384 interpreter unless it names another (the vote pool's vote
+// loop: ovhip/pool.hpp); the per-phase choice is for tests and probes
+#define OVH_VM_RADIX 384
 #include "fpvm.hpp"
+#include "ovhip/pool_remap.hpp"
 #include "keygen.hpp"
 #include "proof.hpp"
 #include "qc_round_groups.hpp"
@@ -61,8 +65,18 @@ static_assert(VM_KZERO == ovh::vm::KZERO && VM_KTAB == ovh::vm::KTAB, "fixed con
 // The inversion's code goes only into the kernels whose program has an `inv` op (vm::run's INV
 // parameter; VM_<PROG>_HAS_INV from the generator): the three final-exponentiation programs. A
 // kernel that binds a program to the interpreter without it says so where it calls vm::run.
-#define VM_ASSERT_NO_INV(P) static_assert(!VM_##P##_HAS_INV, #P " has an inv op: it needs vm::run<SIDE, true>")
-#define VM_ASSERT_INV(P) static_assert(VM_##P##_HAS_INV, #P " has no inv op: bind it to vm::run<SIDE, false>")
+// Either assertion also binds the program's Montgomery radix (VM_<PROG>_RADIX): 2^384, the
+// interpreter vm::run gives by default here. The vote pool names its own (VM_ASSERT_RADIX).
+#define VM_ASSERT_RADIX(P, R) static_assert(VM_##P##_RADIX == (R), #P ": bind it to vm::run<.., RADIX> of its own radix")
+#define VM_ASSERT_NO_INV_ANY_RADIX(P) \
+  static_assert(!VM_##P##_HAS_INV, #P " has an inv op: it needs vm::run<SIDE, true>")
+#define VM_ASSERT_NO_INV(P)      \
+  VM_ASSERT_NO_INV_ANY_RADIX(P); \
+  VM_ASSERT_RADIX(P, OVH_VM_RADIX)
+#define VM_ASSERT_INV(P)                                                                             \
+  static_assert(VM_##P##_HAS_INV, #P " has no inv op: bind it to vm::run<SIDE, false>"); \
+  VM_ASSERT_RADIX(P, OVH_VM_RADIX)
+static_assert(VM_POOL_NCONST <= VM_NCONST, "the pool's constant table fits where the 384 prefix does (SLOT_BASE_W)");
 // the programs that reach kernels through a VmDev chosen by the host (MSM and tree adds, the
 // per-vote programs of the small-batch and same-message paths)
 VM_ASSERT_NO_INV(MADD); VM_ASSERT_NO_INV(PADD); VM_ASSERT_NO_INV(G1PADD);
@@ -1751,11 +1765,12 @@ struct ovh_ctx {
   uint64_t hb_k = 0;
   // Fp-VM programs + constant table in device memory: one member per row of VM_TABLE below, in
   // its order (vm_init uploads them)
-  VmDev vm_vote{}, vm_vote_t{}, vm_fold{}, vm_final{}, vm_rs{}, vm_sigchk{}, vm_pkchk{}, vm_vote1{}, vm_vote_t1{},
+  VmDev vm_vote{}, vm_vote_t{}, vm_fold{}, vm_pfold{}, vm_final{}, vm_rs{}, vm_sigchk{}, vm_pkchk{}, vm_vote1{}, vm_vote_t1{},
       vm_signg0{}, vm_signg1{}, vm_pkgen{}, vm_vote1h{}, vm_vote_t1h{}, vm_qcpre{}, vm_qcmil{}, vm_votew{}, vm_votew_t{},
       vm_votewh{}, vm_votewh_t{}, vm_signg0h{}, vm_final1{}, vm_vsame{}, vm_vsame_t{}, vm_vsame8{}, vm_vsame8_t{},
       vm_h2g{}, vm_gfin{}, vm_g1grp{}, vm_pkdec{}, vm_gmil{}, vm_g1padd{}, vm_madd{}, vm_padd{}, vm_hdbl[5]{};
   uint32_t* vm_consts = nullptr;
+  uint32_t* vm_pool_consts = nullptr;  // the pool's compact table, behind the generated one
   std::vector<void*> vm_bufs;
   // same-message batches (verify_samemsg_locked): per slot the group slab (G_PLANES planes + the
   // H-is-infinity words, gcap entries); OVH_SAMEMSG=0 turns the path off
@@ -1921,6 +1936,7 @@ struct VmProg {
   uint32_t nphases, W, NW;
   const uint16_t* in; uint32_t nin; const uint16_t* out; uint32_t nout;
   const uint32_t* side;
+  bool pool = false;  // a vote pool copy: renumbered to the pool's constant table (ovhip/pool_remap.hpp)
 };
 #define VM_PROG(P, ...) \
   VmProg { VM_##P##_CODE, VM_##P##_NPHASES, VM_##P##_W, VM_##P##_NW, VM_##P##_IN, VM_##P##_NIN, VM_##P##_OUT, VM_##P##_NOUT, __VA_ARGS__ }
@@ -1939,9 +1955,14 @@ struct VmRow {
 #define VM_ROW(member, ...) \
   VmRow { [](ovh_ctx* c) { return &c->member; }, VM_PROG(__VA_ARGS__) }
 static const VmRow VM_TABLE[] = {
-    VM_ROW(vm_vote, VOTE, VM_VOTE_SIDE),
-    VM_ROW(vm_vote_t, VOTE_T, VM_VOTE_T_SIDE),
+    // vote and vote_t run in the pool alone, so their one device copy is the renumbered one: its
+    // constant references are valid against vm_pool_consts only, never against vm_consts
+    VM_ROW(vm_vote, VOTE, VM_VOTE_SIDE, true),
+    VM_ROW(vm_vote_t, VOTE_T, VM_VOTE_T_SIDE, true),
     VM_ROW(vm_fold, FOLD),
+    // the pool's fused fold: this row exists only for the renumbered code (the pool reads .code;
+    // the maps, and a trace buffer under OVH_FLAG_VM_TRACE, are vm_fold's and unused here)
+    VM_ROW(vm_pfold, FOLD, nullptr, true),
     VM_ROW(vm_final, FINAL),
     VM_ROW(vm_rs, RS),
     VM_ROW(vm_sigchk, SIGCHK),
@@ -1989,7 +2010,13 @@ static int vm_upload(ovh_ctx* c, VmDev& d, const VmProg& p) {
   void *dc = nullptr, *di = nullptr, *dout = nullptr;
   HIPCHK(hipMalloc(&dc, (words + pad) * 4));
   c->vm_bufs.push_back(dc);
-  HIPCHK(hipMemcpy(dc, p.code, words * 4, hipMemcpyHostToDevice));
+  if (p.pool) {
+    std::vector<uint32_t> pc(words);
+    if (pool::pool_remap_code(pc.data(), p.code, words, VM_POOL_CONST_IDX, VM_POOL_NCONST)) return OVH_ERR_DEVICE;
+    HIPCHK(hipMemcpy(dc, pc.data(), words * 4, hipMemcpyHostToDevice));
+  } else {
+    HIPCHK(hipMemcpy(dc, p.code, words * 4, hipMemcpyHostToDevice));
+  }
   HIPCHK(hipMemset((uint32_t*)dc + words, 0, pad * 4));
   HIPCHK(hipMalloc(&di, p.nin * 2 + 2));
   c->vm_bufs.push_back(di);
@@ -2031,8 +2058,15 @@ static int vm_upload(ovh_ctx* c, VmDev& d, const VmProg& p) {
 }
 
 static int vm_init(ovh_ctx* c) {
-  HIPCHK(hipMalloc(&c->vm_consts, sizeof(VM_CONST_WORDS)));
+  // the table (every kernel but the pool loads its first VM_NCONST entries), then the pool's own
+  HIPCHK(hipMalloc(&c->vm_consts, sizeof(VM_CONST_WORDS) + (size_t)VM_POOL_NCONST * 48));
   HIPCHK(hipMemcpy(c->vm_consts, VM_CONST_WORDS, sizeof(VM_CONST_WORDS), hipMemcpyHostToDevice));
+  {
+    std::vector<uint32_t> pw((size_t)VM_POOL_NCONST * 12);
+    pool::pool_const_words(pw.data(), VM_CONST_WORDS, VM_POOL_CONST_IDX, VM_POOL_NCONST);
+    c->vm_pool_consts = c->vm_consts + sizeof(VM_CONST_WORDS) / 4;
+    HIPCHK(hipMemcpy(c->vm_pool_consts, pw.data(), pw.size() * 4, hipMemcpyHostToDevice));
+  }
   for (const VmRow& r : VM_TABLE) CHK(vm_upload(c, *r.dev(c), r.prog));
   HIPCHK(hipFuncSetAttribute((const void*)k_vm_pool, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_POOL));
   HIPCHK(hipFuncSetAttribute((const void*)k_vm_signg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_SIGNG));
@@ -2391,8 +2425,8 @@ static int batch_front(ovh_ctx* c, int slot, uint32_t n, const uint8_t* d_sigs, 
   pa.pv_side = c->vm_vote.side;
   pa.pt_code = c->vm_vote_t.code;
   pa.pt_side = c->vm_vote_t.side;
-  pa.fold_code = c->vm_fold.code;
-  pa.cst = c->vm_consts;
+  pa.fold_code = c->vm_pfold.code;
+  pa.cst = c->vm_pool_consts;
   for (uint32_t par = 0; launch && par < (shard ? c->shard_streams : 2u); ++par) {
     // the shard path without reserved CUs: one grid of this batch alone per batch, on the pool
     // streams in turn (its workgroups leave when the batch is claimed, so the caller's collective
@@ -3925,6 +3959,8 @@ int ovh_vm_trace(ovh_ctx* c, int prog, uint64_t* stamps, size_t max) {
   if (!(c->flags & OVH_FLAG_VM_TRACE)) return 0;
   std::lock_guard<std::mutex> g(c->mu);
   if (hipSetDevice(c->device) != hipSuccess) return -OVH_ERR_DEVICE;
+  // (vm_vote / vm_vote_t: only their trace and phase count are read here; their code is the
+  // pool's renumbered copy and pairs with vm_pool_consts alone)
   const VmDev* d = prog == 0 ? &c->vm_vote : prog == 1 ? &c->vm_fold : prog == 2 ? &c->vm_final : &c->vm_vote_t;
   const size_t n = (size_t)d->nphases + 1, k = max < n ? max : n;
   if (sync_all(c) || (k && hipMemcpy(stamps, d->trace, k * 8, hipMemcpyDeviceToHost) != hipSuccess))
@@ -3938,7 +3974,7 @@ int ovh_vm_clock(ovh_ctx* c, uint64_t* stamps, size_t max) {
   if (!(c->flags & OVH_FLAG_VM_CLOCK)) return 0;
   std::lock_guard<std::mutex> g(c->mu);
   if (hipSetDevice(c->device) != hipSuccess || sync_all(c)) return -OVH_ERR_DEVICE;
-  const VmDev* d = c->clk_table ? &c->vm_vote_t : &c->vm_vote;
+  const VmDev* d = c->clk_table ? &c->vm_vote_t : &c->vm_vote;  // (the clock stamps only: see ovh_vm_trace)
   const size_t n = (size_t)2 * c->clk_wgs, k = max < n ? max : n;
   if (k && hipMemcpy(stamps, d->clk, k * 8, hipMemcpyDeviceToHost) != hipSuccess) return -OVH_ERR_DEVICE;
   return (int)n;

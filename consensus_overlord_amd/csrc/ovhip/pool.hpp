@@ -122,7 +122,8 @@ __global__ void k_stamp(uint64_t* p, uint64_t v) {
 }
 
 // The pool kernel's arguments: the queue, the descriptors, the two vote programs' instruction
-// and side-word streams, the fold program, the constant table and the spill scratch. Everything
+// and side-word streams, the fold program (all three renumbered to the pool's constant table,
+// `cst`: ovhip/pool_remap.hpp) and the spill scratch. Everything
 // per batch is in the descriptor and read where it is used.
 struct PoolArgs {
   uint64_t* q;
@@ -340,8 +341,13 @@ __device__ __forceinline__ T* unip(T* p) {
 #endif
 __device__ __forceinline__ void vote_quad(const PoolArgs& a, uint32_t slot_in, uint32_t quad_in, uint32_t* lds,
                                           const bool TABLE) {
-  VM_ASSERT_NO_INV(VOTE);
-  VM_ASSERT_NO_INV(VOTE_T);
+  // the vote loop's interpreter: no inversion, radix 2^392 (products without the conditional
+  // subtraction, fpvm.hpp); the programs convert at their own edges (tools/fpvm/progs.py), so the
+  // prologue, the epilogue, the fused fold and every plane keep value * 2^384
+  VM_ASSERT_NO_INV_ANY_RADIX(VOTE);
+  VM_ASSERT_NO_INV_ANY_RADIX(VOTE_T);
+  VM_ASSERT_RADIX(VOTE, 392);
+  VM_ASSERT_RADIX(VOTE_T, 392);
   const uint32_t NSLOTS = TABLE ? VM_VOTE_T_NSLOTS : VM_VOTE_NSLOTS;
   const uint32_t STRIDE = TABLE ? VOTE_T_STRIDE_W : VOTE_STRIDE_W;
   const uint32_t NPH = TABLE ? VM_VOTE_T_NPHASES : VM_VOTE_NPHASES;
@@ -416,7 +422,7 @@ __device__ __forceinline__ void vote_quad(const PoolArgs& a, uint32_t slot_in, u
     }
     __syncthreads();
     const uint64_t scalar = vote_scalar(uni64(dget(&bd->seed)), uni64(dget(&bd->base)), i);
-    vm::run<true, false, OVH_POOL_UNROLL>(
+    vm::run<true, false, OVH_POOL_UNROLL, 392>(
         TABLE ? a.pt_code : a.pv_code, NPH, VM_VOTE_W, lane, active, slots, cst, scalar, vm::Out{s.p, s.cap, i},
         nullptr, TABLE ? a.pt_side : a.pv_side,
         a.scr + (size_t)blockIdx.x * VM_SLICES * VOTE_NSCR * 12 + slice * VOTE_NSCR * 12);
@@ -511,7 +517,7 @@ __global__ __launch_bounds__(64, 2) void k_vm_pool(PoolArgs a) {
   // reserved CUs (OVH_FLAG_POOL_RESERVE): simd_key bits 2..8 = SE | SA | CU (wave-uniform)
   if (a.skip_cu && ((simd_key() >> 2) & 0x7Fu) < a.skip_cu) return;
   uint32_t* lds = reinterpret_cast<uint32_t*>(lds4);
-  load_consts(lds, a.cst, VM_NCONST);
+  load_consts(lds, a.cst, VM_POOL_NCONST);  // the pool's own table (ovhip/pool_remap.hpp)
   const uint64_t t_in = __builtin_amdgcn_s_memrealtime();
   vote_stagger();
   uint32_t nquads = 0, why = 0;

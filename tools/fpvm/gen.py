@@ -96,26 +96,95 @@ def build_all():
     # terms (fpvm.hpp lin_sum: -x enters as ~x, and ~x + 2p + 1 = 2p - x mod 2^384)
     for n in range(5):
         assert consts.ref(n * (2 * P + 1), True) - sched.CONST_BASE == KTAB + n
+    # The radix-392 programs are built last, when the table's 384 prefix is complete and a wide
+    # entry's index is final (sched.ConstTable); in their own turn only their radix-384 twins
+    # register their constants in the prefix (sched.seed_prefix)
     out = {}
-    for name, (builder, ins, outs) in progs.PROGRAMS.items():
-        prog = builder()
-        prog.fuse()
-        bias = {i: SEC_BIAS[name][op.sec] for i, op in enumerate(prog.ops)
-                if name in SEC_BIAS and op.sec in SEC_BIAS[name]}
-        sc = sched.schedule(prog, WIDTH[name], consts, max_slots=MAX_SLOTS.get(name, 256), heavy_w=HEAVY_W.get(name, 2),
-                            hoist=HOIST.get(name), stretch=STRETCH.get(name, 1.3), mixed=name not in NOMIX,
-                            bias=bias or None, spill_k=SPILL_K.get(name) or None, defer=DEFER.get(name),
-                            families=name in FAMILIES)
-        words = sched.encode(sc)
-        out[name] = (prog, sc, words, ins, outs)
+    for name, (builder, _, _) in progs.PROGRAMS.items():
+        if name in progs.WIDE_PROGRAMS:
+            twin = builder(radix=384)
+            twin.fuse()
+            sched.seed_prefix(twin, consts)
+            out[name] = None
+        else:
+            out[name] = build_one(consts, name)
+    for name in progs.WIDE_PROGRAMS:
+        out[name] = build_one(consts, name)
     return consts, out
+
+
+def build_one(consts, name):
+    """Trace, fuse, schedule and encode program `name` against the table `consts`."""
+    builder, ins, outs = progs.PROGRAMS[name]
+    prog = builder()
+    prog.fuse()
+    bias = {i: SEC_BIAS[name][op.sec] for i, op in enumerate(prog.ops)
+            if name in SEC_BIAS and op.sec in SEC_BIAS[name]}
+    sc = sched.schedule(prog, WIDTH[name], consts, max_slots=MAX_SLOTS.get(name, 256), heavy_w=HEAVY_W.get(name, 2),
+                        hoist=HOIST.get(name), stretch=STRETCH.get(name, 1.3), mixed=name not in NOMIX,
+                        bias=bias or None, spill_k=SPILL_K.get(name) or None, defer=DEFER.get(name),
+                        families=name in FAMILIES)
+    words = sched.encode(sc)
+    return (prog, sc, words, ins, outs)
+
+
+def pool_table(consts, built):
+    """The vote pool's compact constant table (ovhip/pool.hpp loads it in place of the prefix):
+    -> table indices of its entries, in pool order: the fixed entries, what the fold fused into
+    the pool refers to beyond them, zero entries as padding, then the wide programs' entries.
+    The padding puts wide entry k at a pool index congruent to its table index modulo
+    sched.BANK_MOD, so the LDS bank residues the slot allocation modelled for vote / vote_t
+    (constant c in residue c mod BANK_MOD) are the pool's."""
+    nfix, npre = sched.NFIXED, len(consts.entries)
+    fwords = built["fold"][2]
+    extra = []
+    for k in range(0, len(fwords), 4):
+        for w in (fwords[k + 1], fwords[k + 2]):
+            for h in (w & 0xFFFF, w >> 16):
+                c = h & (sched.CONST_BASE - 1)
+                if h & sched.CONST_BASE and c >= nfix and c not in extra:
+                    extra.append(c)
+    assert all(c < npre for c in extra), "fold is a radix-384 program"
+    head = list(range(nfix)) + sorted(extra)
+    head += [KZERO] * ((npre - len(head)) % sched.BANK_MOD)
+    return head + [npre + k for k in range(len(consts.wide))]
+
+
+def pool_remap(pool_idx, words, nconst_all):
+    """Instruction words in table numbering -> the pool table's numbering (the function
+    ovhip/pool_remap.hpp applies to the pool's copies of vote, vote_t and fold at upload);
+    raises on a reference to an entry the pool table lacks."""
+    inv = {}
+    for k, g in enumerate(pool_idx):
+        inv.setdefault(g, k)   # (padding repeats the zero entry: its first place)
+    out = list(words)
+
+    def m(h):
+        if not h & sched.CONST_BASE:
+            return h
+        c = h & (sched.CONST_BASE - 1)
+        assert c < nconst_all
+        return (h & ~(sched.CONST_BASE - 1)) | inv[c]
+    for k in range(0, len(out), 4):
+        for j in (1, 2):
+            out[k + j] = m(out[k + j] & 0xFFFF) | m(out[k + j] >> 16) << 16
+    return out
 
 
 def emit(consts, built, path):
     lines = ["// GENERATED by tools/fpvm/gen.py -- do not edit. Fp-VM programs for libovhip.", "#pragma once",
              "#include <stdint.h>", ""]
     cw = consts.words()
-    lines.append("#define VM_NCONST %d" % len(cw))
+    # VM_NCONST: the radix-384 prefix, what every kernel but the vote pool loads into LDS; the
+    # wide programs' entries follow it (VM_NCONST_ALL in all). The pool loads a compact table of
+    # VM_POOL_NCONST entries instead, entry k = table entry VM_POOL_CONST_IDX[k], and runs copies
+    # of vote / vote_t / fold renumbered to it (ovhip/pool_remap.hpp)
+    pidx = pool_table(consts, built)
+    assert len(pidx) <= len(consts.entries), "the pool's constant table outgrew the 384 prefix (LDS)"
+    lines.append("#define VM_NCONST %d" % len(consts.entries))
+    lines.append("#define VM_NCONST_ALL %d" % len(cw))
+    lines.append("#define VM_POOL_NCONST %d" % len(pidx))
+    lines.append("static const uint16_t VM_POOL_CONST_IDX[%d] = {%s};" % (len(pidx), ", ".join(map(str, pidx))))
     lines.append("#define VM_KZERO %d" % KZERO)
     lines.append("#define VM_KTAB %d" % KTAB)
     for k in ("S_U", "S_SIG", "S_TAU", "S_F", "S_RS", "S_TOTAL", "G_U", "G_H", "G_F", "G_PLANES"):
@@ -139,6 +208,9 @@ def emit(consts, built, path):
         # whether the program runs an inversion: the kernels of programs without one bind an
         # interpreter without the inversion's code (fpvm.hpp run<SIDE, INV>)
         lines.append("#define VM_%s_HAS_INV %d" % (N, int(any(op.kind == "inv" for op in prog.ops))))
+        # the program's Montgomery radix: the interpreter a kernel binds it to must run that one
+        # (fpvm.hpp run<.., RADIX>)
+        lines.append("#define VM_%s_RADIX %d" % (N, prog.radix))
         slot_in = [sc.slot_of.get(prog.inputs[n], 0xFFFF) for n in ins]
         slot_out = [sc.slot_of[prog.outputs[n]] for n in outs]
         st = {prog.ops[v].name: prog.ops[v].imm for n, v in prog.outputs.items() if prog.ops[v].kind == "st"}

@@ -126,9 +126,18 @@ FORM_COST = {"unit": 1, "scaled": 2, "acc": 6} if os.environ.get("OVH_GEN_UNITLI
 class Prog:
     """A traced program. ops[i] defines value i. kind 'in' = input, 'const' = constant."""
 
-    def __init__(self, name, lin_width: int = LIN_WIDTH):
+    def __init__(self, name, lin_width: int = LIN_WIDTH, radix: int = 384):
         self.name = name
         self.lin_width = lin_width   # operands of a lin op (8: the 32-byte instruction format)
+        # Montgomery radix 2^radix of the program's products and constants (fpvm.hpp): 384, or 392
+        # ("wide": the vote pool's programs). Slots and HBM planes outside a program are always
+        # value * 2^384, so a wide program converts at its own edges (progs.py) and sees a field
+        # input as value * 2^-8 (edge_scales); flag inputs (raw_inputs) are plain 0 / 1.
+        assert radix in (384, 392), radix
+        self.radix = radix
+        self.raw_inputs = set()
+        # list-scheduling priority offsets per section (sched.schedule), travelling with the program
+        self.sec_bias = {}
         self.ops = []
         self.outputs = {}
         self.inputs = {}
@@ -144,10 +153,21 @@ class Prog:
         self.ops.append(op)
         return Val(self, len(self.ops) - 1)
 
-    def input(self, name):
+    def input(self, name, raw=False):
+        """raw: a flag the prologue writes as plain limbs (0 / 1), not a field element"""
         v = self._new(Op("in", name=name))
         self.inputs[name] = v.id
+        if raw:
+            self.raw_inputs.add(name)
         return v
+
+    def edge_scales(self):
+        """(s_in, s_out): evaluate / sched.simulate take field inputs and give `st` outputs as the
+        values the caller means (slot and plane limbs = value * 2^384). Inside a radix-392 program
+        such a slot is the value * 2^-8, and a stored value v reads outside as v * 2^8."""
+        if self.radix == 384:
+            return 1, 1
+        return pow(2, 384 - self.radix, P), pow(2, self.radix - 384, P)
 
     def const(self, value: int):
         value %= P
@@ -393,7 +413,9 @@ class Prog:
 
     # ------------------------------------------------------------------ evaluation
     def evaluate(self, inputs: dict, scalar: int = 0) -> list:
-        """Evaluate every value with Python integers (canonical values, not Montgomery)."""
+        """Evaluate every value with Python integers (canonical values, not Montgomery). Field
+        inputs and `st` values are the caller's (edge_scales)."""
+        s_in, s_out = self.edge_scales()
         vals = [None] * len(self.ops)
         # fill ops (sched.spill_pass) are appended after their readers: each takes its original
         # value's (deps[0]) as soon as that is known
@@ -405,6 +427,10 @@ class Prog:
             if op.kind == "fill":
                 continue
             vals[i] = eval_op(op, vals, inputs, scalar)
+            if op.kind == "in" and op.name not in self.raw_inputs:
+                vals[i] = vals[i] * s_in % P
+            elif op.kind == "st":
+                vals[i] = vals[i] * s_out % P
             for f in fills.get(i, ()):
                 vals[f] = vals[i]
         return vals

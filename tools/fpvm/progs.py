@@ -88,19 +88,68 @@ def affine_pair(a, Q):
     return [Q[0][0], Q[0][1], Q[1][0], Q[1][1], T[0][0], T[0][1], T[1][0], T[1][1]]
 
 
-def build_vote():
-    p = Prog("vote")
+# The pool's two programs run in radix 2^392 (fpvm.hpp: products without the conditional
+# subtraction) and convert at their own edges, so everything around them keeps value * 2^384:
+#   raw inputs (pk_x, sig_x*: plain limbs x)  one product by the constant 2^392 (where a 384
+#                                             program multiplies by 2^384): x * 2^392 in the slot;
+#   field inputs (u.., vote_t's key: v 2^384) one product by the constant 2^8 (limbs 2^400):
+#                                             v 2^384 * 2^400 / 2^392 = v 2^392;
+#   stored values (f0..f11, q0..q3, t0..t3)   one product by the constant 2^-8 (limbs 2^384):
+#                                             v 2^392 * 2^384 / 2^392 = v 2^384, which `st`
+#                                             canonicalises as before.
+# vote_t's projective key (X, Y, Z) 2^384 read as radix-392 values is (X, Y, Z) 2^-8, the same
+# point; it is converted all the same (three products of ~16.7 k), so that r pk, the Miller
+# loop's lines and the stored f are value for value what the radix-384 program computed, not
+# that times a power of 2^-8 the final exponentiation would remove.
+WIDE = 392
+# (radix=384 builds the twin without the conversions: the program of before, which gen.py traces
+# only to keep the constant table's radix-384 prefix what it was, sched.seed_prefix.)
+
+
+def _edges(p):
+    """(R, field-input conversion, stored-value conversion) of program p's radix"""
+    R = p.const(pow(2, p.radix, P))           # times a raw input x: the value x
+    if p.radix == 384:
+        return R, (lambda v: v), (lambda v: v)
+    K = p.const(pow(2, p.radix - 384, P))     # times a field input (seen as v 2^-8): v
+    S = None
+
+    def conv_st(v):
+        nonlocal S
+        if S is None:
+            S = p.const(pow(2, 384 - p.radix, P))   # times a value v: v 2^-8, stored as v 2^384
+        return p.muls(v, 0, None, S, 0, None)
+    return R, (lambda v: v * K), conv_st
+
+
+def _store_all(p, fst, vals):
+    """The stored planes (VOTE_ST: f, sigma, tau), each through the radix's conversion. A
+    conversion product feeds nothing but its `st`, whose priority (10^6: stores free their slot,
+    sched.schedule) it would inherit -- and open a product phase of its own the moment it is
+    ready. The section's offset puts it back among the ordinary products, into idle lanes: vote
+    2,725 -> 2,719 phases (2,716 in radix 384)."""
+    if p.radix != 384:
+        p.sec_bias["conv"] = -10 ** 6
+    sec, p.section = getattr(p, "section", None), "conv"
+    conv = [fst(v) for v in vals]
+    p.section = sec
+    for (name, plane), v in zip(VOTE_ST, conv):
+        p.store(name, v, plane)
+
+
+def build_vote(radix=WIDE):
+    p = Prog("vote", radix=radix)
     a = Alg(p, use_sop=USE_SOP, fast_sqrt=FAST_SQRT_BATCH)
-    R = p.const(R_MONT)
+    R, fin, fst = _edges(p)
     pkx = p.input("pk_x") * R
     sx = (p.input("sig_x0") * R, p.input("sig_x1") * R)
-    u0 = (p.input("u00"), p.input("u01"))
-    u1 = (p.input("u10"), p.input("u11"))
-    pk_ok, (px, py) = a.g1_decompress(pkx, p.input("pk_sort"))
+    u0 = (fin(p.input("u00")), fin(p.input("u01")))
+    u1 = (fin(p.input("u10")), fin(p.input("u11")))
+    pk_ok, (px, py) = a.g1_decompress(pkx, p.input("pk_sort", raw=True))
     Pp = (px, py, p.one)
     pk_grp, _ = a.g1_in_group(Pp)
     p.section = "sig"   # the signature's decompression + subgroup check (gen.py SEC_BIAS)
-    sig_ok, (qx, qy) = a.g2_decompress(sx, p.input("sig_sort"))
+    sig_ok, (qx, qy) = a.g2_decompress(sx, p.input("sig_sort", raw=True))
     Qs = (qx, qy, (p.one, p.zero))
     sig_grp = a.g2_in_group(Qs)
     p.section = None
@@ -110,8 +159,7 @@ def build_vote():
     f = a.miller_loop(rP, H)
     for name, v in zip(VOTE_OUT, [pk_ok, pk_grp, sig_ok, sig_grp, h_inf]):
         p.output(name, v)
-    for (name, plane), v in zip(VOTE_ST, flat12(f) + affine_pair(a, Qs)):
-        p.store(name, v, plane)
+    _store_all(p, fst, flat12(f) + affine_pair(a, Qs))
     return p
 
 
@@ -119,16 +167,16 @@ VOTE_T_IN = ["pk_X", "pk_Y", "pk_Z", "sig_x0", "sig_x1", "sig_sort", "u00", "u01
 VOTE_T_OUT = ["sig_ok", "sig_grp", "h_inf"]
 
 
-def build_vote_t():
-    p = Prog("vote_t")
+def build_vote_t(radix=WIDE):
+    p = Prog("vote_t", radix=radix)
     a = Alg(p, use_sop=USE_SOP, fast_sqrt=FAST_SQRT_BATCH)
-    R = p.const(R_MONT)
-    Pp = (p.input("pk_X"), p.input("pk_Y"), p.input("pk_Z"))
+    R, fin, fst = _edges(p)
+    Pp = (fin(p.input("pk_X")), fin(p.input("pk_Y")), fin(p.input("pk_Z")))
     sx = (p.input("sig_x0") * R, p.input("sig_x1") * R)
-    u0 = (p.input("u00"), p.input("u01"))
-    u1 = (p.input("u10"), p.input("u11"))
+    u0 = (fin(p.input("u00")), fin(p.input("u01")))
+    u1 = (fin(p.input("u10")), fin(p.input("u11")))
     p.section = "sig"   # the signature's decompression + subgroup check (gen.py SEC_BIAS)
-    sig_ok, (qx, qy) = a.g2_decompress(sx, p.input("sig_sort"))
+    sig_ok, (qx, qy) = a.g2_decompress(sx, p.input("sig_sort", raw=True))
     Qs = (qx, qy, (p.one, p.zero))
     sig_grp = a.g2_in_group(Qs)
     p.section = None
@@ -138,8 +186,7 @@ def build_vote_t():
     f = a.miller_loop(rP, H)
     for name, v in zip(VOTE_T_OUT, [sig_ok, sig_grp, h_inf]):
         p.output(name, v)
-    for (name, plane), v in zip(VOTE_ST, flat12(f) + affine_pair(a, Qs)):
-        p.store(name, v, plane)
+    _store_all(p, fst, flat12(f) + affine_pair(a, Qs))
     return p
 
 
@@ -653,6 +700,7 @@ def build_final():
     return p
 
 
+WIDE_PROGRAMS = ("vote", "vote_t")   # built in radix 2^392 (gen.build_all builds them last)
 PROGRAMS = {
     "vote": (build_vote, VOTE_IN, VOTE_OUT),
     "vote_t": (build_vote_t, VOTE_T_IN, VOTE_T_OUT),

@@ -14,6 +14,7 @@ Instruction (4 x uint32 per lane per phase):
   w3 = ca | cb << 5 | cc << 10 | cd << 15   (5-bit two's-complement coefficients)
        (sop: z = A C + cb B D)
        | k << 20 (lin: k * (unit sum) when 2 <= k <= 15, ir.lin_form "scaled")
+       | FORCE_ACC (bit 24, lin) | WIDE (bit 25, product ops of a radix-2^392 program)
   operand: slot index (< CONST_BASE) or CONST_BASE + k (constant table entry k); a missing
   operand is the zero constant with coefficient 0, so every lane loads four operands.
 """
@@ -51,30 +52,71 @@ ALL_ACC = os.environ.get("OVH_GEN_UNITLIN", "0") != "1"
 # FORCE_ACC bit). 0 restores ALL_ACC's one-block-per-phase rule in every phase.
 PHASE_UNIT = os.environ.get("OVH_GEN_PHASE_UNIT", "1") == "1"
 FORCE_ACC = 1 << 24   # w3 bit: run this lin op in the general-coefficient block
+WIDE = 1 << 25        # w3 bit: a product op of a radix-2^392 program (fpvm.hpp W_WIDE)
 R_MONT = pow(2, 384, P)
+RADIX_BITS = (384, 392)
+NFIXED = 7            # the fixed entries (gen.build_all: plain 1, zero, KTAB + 0..4), radix-free
 
 
 class ConstTable:
     """Constants shared by every program: (value, raw) -> index. raw constants are stored as
-    plain limbs; the others in Montgomery form (value * 2^384 mod p)."""
+    plain limbs; the others in Montgomery form (value * 2^radix mod p, the radix of the program
+    that refers to them).
+
+    Layout. `entries` is the table of the radix-384 programs, in order of first reference: the
+    NFIXED fixed entries first (raw limbs or zero: the same in every radix). The constants of the
+    radix-392 programs (ir.Prog.radix) form a list of their own, `wide`, that follows the 384
+    entries in the table (words(), all_entries()): the prefix -- what every kernel but the vote
+    pool loads -- does not depend on which programs are wide. A wide entry's index is final when
+    it is given, so the first one closes the prefix: gen.build_all builds the wide programs after
+    every 384 program, and a new 384 constant after that is an error.
+    The 384 form of a wide program's constants keeps its place in `entries` (seed_prefix, from
+    the program's radix-384 twin), so the indices, slot allocation and code of every 384 program
+    are what they are in a table of 384 programs alone."""
 
     def __init__(self):
         self.index = {}
         self.entries = []
+        self.wide_index = {}
+        self.wide = []
 
-    def ref(self, value, raw):
+    def ref(self, value, raw, radix=384):
+        assert radix in RADIX_BITS, radix
         key = (value, bool(raw))
+        if radix == 392:
+            if self.index.get(key, NFIXED) < NFIXED and (raw or value == 0):
+                return CONST_BASE + self.index[key]
+            if key not in self.wide_index:
+                self.wide_index[key] = len(self.wide)
+                self.wide.append(key)
+            return CONST_BASE + len(self.entries) + self.wide_index[key]
         if key not in self.index:
+            assert not self.wide, "a new radix-384 constant after the first radix-392 one: the prefix is closed"
             self.index[key] = len(self.entries)
             self.entries.append(key)
         return CONST_BASE + self.index[key]
 
+    def all_entries(self):
+        """(value, raw, radix) of every table entry, in table order"""
+        return [(v, r, 384) for v, r in self.entries] + [(v, r, 392) for v, r in self.wide]
+
     def words(self):
         out = []
-        for value, raw in self.entries:
-            v = value if raw else value * R_MONT % P
+        for value, raw, radix in self.all_entries():
+            v = value if raw else value * pow(2, radix, P) % P
             out.append([(v >> (32 * k)) & 0xFFFFFFFF for k in range(12)])
         return out
+
+
+def seed_prefix(twin, consts: ConstTable):
+    """Register the constants of `twin` -- the radix-384 build of a wide program, traced and
+    fused like it -- in the 384 prefix, in the order schedule() would (its first pass over the
+    program's constants), so the prefix is the one a table of 384 programs alone has."""
+    ops = twin.ops
+    pre = {i for i in twin.live_ops() if ops[i].kind in ("in", "const")}
+    for i in pre:
+        if ops[i].kind == "const":
+            consts.ref(ops[i].imm, ops[i].name == "raw")
 
 
 class Scheduled:
@@ -106,6 +148,7 @@ def schedule(prog, W, consts: ConstTable, max_slots=None, heavy_w=10, light_w=1,
              hoist=None, stretch=1.3, split_sop=False, dual=False, bias=None, light_margin=0, spill_k=None,
              defer=None, families=False):
     ops = prog.ops
+    radix = getattr(prog, "radix", 384)
     live = prog.live_ops()
     liveset = set(live)
     pre = {i for i in live if ops[i].kind in ("in", "const")}
@@ -128,6 +171,13 @@ def schedule(prog, W, consts: ConstTable, max_slots=None, heavy_w=10, light_w=1,
         for i in work:
             if ops[i].kind != "st":
                 prio[i] += bias.get(i, 0)
+    # a program's own offsets per section (ir.Prog.sec_bias): part of the program, so every
+    # schedule of it -- gen.py's and a test's -- orders it alike
+    sec_bias = getattr(prog, "sec_bias", None)
+    if sec_bias:
+        for i in work:
+            if ops[i].kind != "st":
+                prio[i] += sec_bias.get(ops[i].sec, 0)
     # release phase: an op may not run more than `hoist` phases before the earliest phase its
     # first consumer could run (ASAP depth x the schedule's expected stretch), so values that
     # are ready early but needed late (the per-step addends of a scalar-multiplication chain)
@@ -285,7 +335,7 @@ def schedule(prog, W, consts: ConstTable, max_slots=None, heavy_w=10, light_w=1,
     # new slot only when none is free).
     for i in pre:
         if ops[i].kind == "const":
-            consts.ref(ops[i].imm, ops[i].name == "raw")
+            consts.ref(ops[i].imm, ops[i].name == "raw", radix)
     zero_c = consts.ref(0, False) - CONST_BASE
     lane_of = {}
     reads = defaultdict(set)
@@ -301,7 +351,7 @@ def schedule(prog, W, consts: ConstTable, max_slots=None, heavy_w=10, light_w=1,
                 if v is not None and ops[v].kind != "const":
                     reads[v].add((t, g, pos))
                     continue
-                c = zero_c if v is None else consts.ref(ops[v].imm, ops[v].name == "raw") - CONST_BASE
+                c = zero_c if v is None else consts.ref(ops[v].imm, ops[v].name == "raw", radix) - CONST_BASE
                 if (t, g, pos, c) not in seen_c:
                     seen_c.add((t, g, pos, c))
                     use[(t, g, pos)][c % BANK_MOD] += 1
@@ -348,7 +398,7 @@ def schedule(prog, W, consts: ConstTable, max_slots=None, heavy_w=10, light_w=1,
                       lane_of if WBANK else None)
     for i in pre:
         if ops[i].kind == "const":
-            consts.ref(ops[i].imm, ops[i].name == "raw")
+            consts.ref(ops[i].imm, ops[i].name == "raw", radix)
     sc = Scheduled(prog, W, rounds, slot_of, nslots, consts)
     sc.kinds = kinds
     sc.nscr, sc.nspill, sc.nfill = nscr, nspill, nfill
@@ -378,7 +428,8 @@ def improve_banks(prog, rounds, slot_of, def_round, last_use, nslots, consts, pa
                     key = ("v", v)
                     reads_of[v].add((t, pos))
                 else:
-                    c = zero_c if v is None else consts.ref(ops[v].imm, ops[v].name == "raw") - CONST_BASE
+                    c = zero_c if v is None else consts.ref(ops[v].imm, ops[v].name == "raw",
+                                                            getattr(prog, "radix", 384)) - CONST_BASE
                     key = ("c", c)
                 if key not in ctx[(t, pos)]:
                     ctx[(t, pos)].append(key)
@@ -461,7 +512,7 @@ def _operand(sc, v):
         return sc.consts.ref(0, False)
     op = sc.prog.ops[v]
     if op.kind == "const":
-        return sc.consts.ref(op.imm, op.name == "raw")
+        return sc.consts.ref(op.imm, op.name == "raw", getattr(sc.prog, "radix", 384))
     return sc.slot_of[v]
 
 
@@ -560,6 +611,7 @@ def encode(sc):
     """-> list of uint32 words, nphases * W * words_per_lane."""
     words = []
     ops = sc.prog.ops
+    radix = getattr(sc.prog, "radix", 384)
     nw = words_per_lane(sc.prog)
     LW = sc.prog.lin_width
     sc.side_words = []
@@ -598,6 +650,8 @@ def encode(sc):
             if k in ("sgn0", "lex", "eq"):
                 cref = sc.consts.ref(1, True)          # plain 1: from-Montgomery product
             elif k == "inv":
+                # (fpvm.hpp fp_inv closes with a 384-form product: no inversion in a wide program)
+                assert radix == 384, "%s: inv in a radix-%d program" % (sc.prog.name, radix)
                 cref = sc.consts.ref(R_MONT * R_MONT % P, False)   # raw R^3: back to Montgomery
             else:
                 cref = _operand(sc, C)
@@ -614,6 +668,8 @@ def encode(sc):
             w3 = _c5(coefs[0]) | _c5(coefs[1]) << 5 | _c5(coefs[2]) << 10 | _c5(coefs[3]) << 15 | scale << 20
             if k == "lin" and not unit and ALL_ACC:
                 w3 |= FORCE_ACC
+            if k in PRODUCTS and radix == 392:
+                w3 |= WIDE
             words += [w0, xa | xb << 16, cref | dref << 16, w3]
         # the phase header (wave-uniform code paths) in bits 22.. of every lane's w0
         base = len(words) - sc.W * nw
@@ -625,6 +681,14 @@ def encode(sc):
         # phase in the general block): no phase may mix unit-block and general-block lin ops
         if hdr & H_ACC:
             assert not any(b & H_LIN and not b & H_SELB for b in lane_bits), (sc.prog.name, "mixed lin blocks")
+            # and a lin lane stores from the general block only with FORCE_ACC (exec tests the bit,
+            # not the coefficients): without it the op would lose its store
+            for lane in range(sc.W):
+                w = words[base + lane * nw:base + lane * nw + 4]
+                assert (w[0] & 31) != OPC["lin"] or w[3] & FORCE_ACC, (sc.prog.name, "acc-form lin without FORCE_ACC")
+        # a wide program's product phases: exec reads the radix from the first lane's w3
+        if radix == 392 and hdr & H_MUL:
+            assert words[base + 3] & WIDE, (sc.prog.name, "lane 0 of a product phase is no product op")
         for lane in range(sc.W):
             words[base + lane * nw] |= hdr
     return words
@@ -662,11 +726,15 @@ def _s5(x):
 
 def simulate(sc, words, inputs: dict, scalar: int = 0):
     """Execute the encoded stream on canonical values; returns {output name: value}."""
-    const_vals = sc.consts.entries
+    const_vals = sc.consts.all_entries()
+    # a wide program sees its field inputs (value * 2^384 in the slot) as value * 2^-8 and scales
+    # what it stores back (ir.Prog.evaluate)
+    s_in, s_out = sc.prog.edge_scales() if hasattr(sc.prog, "edge_scales") else (1, 1)
     slots = [0] * sc.nslots
     for name, v in sc.prog.inputs.items():
         if v in sc.slot_of:
-            slots[sc.slot_of[v]] = inputs[name] % P
+            raw = name in getattr(sc.prog, "raw_inputs", ())
+            slots[sc.slot_of[v]] = inputs[name] % P * (1 if raw else s_in) % P
 
     def get(ref):
         if ref >= CONST_BASE:
@@ -706,7 +774,7 @@ def simulate(sc, words, inputs: dict, scalar: int = 0):
             elif opc in (OPC["and"], OPC["or"], OPC["xor"]):
                 z = (A & C) if opc == OPC["and"] else (A | C) if opc == OPC["or"] else (A ^ C)
             elif opc == OPC["st"]:
-                stored[imm] = A
+                stored[imm] = A * s_out % P
                 continue
             elif opc == OPC["inv"]:
                 z = pow(A, P - 2, P)

@@ -10,6 +10,10 @@ v_mad_u64_u32 issues in ~5.4 cycles per wave, other VALU ops in 4. The 12 x 32 f
 one mad and the column shift is one v_lshrrev_b64: 392 mads + 14 x (mul_lo, and) + 13 ands +
 27 shifts. The split of the inputs into 28-bit limbs (a shifted left by 8: with R = 2^392 the
 result is a b 2^-384), the join back to 12 x 32 and the final conditional subtraction are C++.
+
+The wide form fp_mul28w_gfx950 is the same one-accumulator schedule with neither operand shifted
+(r = a b 2^-392) and a join without the subtraction: for a, b < 4p the result is below 1.0064 p.
+There is no two-accumulator wide variant.
 """
 import os
 
@@ -89,14 +93,16 @@ def body_2acc():
     return lines, ["v250", "v251", "v252", "v253"]
 
 
-def emit_fn(e, name, lines, clob):
+def emit_fn(e, name, lines, clob, wide=False):
+    """wide: R = 2^392 kept (no operand shifted, r = a b 2^-392 < 1.0064 p for a, b < 4p: no
+    conditional subtraction in the join)."""
     outs = ['[m%d] "=&v"(m[%d])' % (i, i) for i in range(N)] + ['[t%d] "=&v"(t[%d])' % (i, i) for i in range(N)]
     ins = ['[x%d] "v"(x[%d])' % (i, i) for i in range(N)] + ['[y%d] "v"(y[%d])' % (i, i) for i in range(N)] + \
         ['[p%d] "s"(P28[%d])' % (i, i) for i in range(N)] + ['[pinv] "s"(PINV28)', '[mask] "v"(M28)']
     e("__device__ __forceinline__ void %s(uint32_t* __restrict__ r, const uint32_t* __restrict__ a," % name)
     e("%s const uint32_t* __restrict__ b) {" % (" " * (len(name) + 24)))
     e("  uint32_t x[14], y[14], m[14], t[14];")
-    e("  split28<8>(x, a);")
+    e("  split28<%d>(x, a);" % (0 if wide else 8))
     e("  split28<0>(y, b);")
     e("  asm volatile(")
     for k in range(0, len(lines), 8):
@@ -105,7 +111,7 @@ def emit_fn(e, name, lines, clob):
     e("      : " + ", ".join(ins))
     e('      : "vcc", %s);' % ", ".join('"%s"' % c for c in clob))
     e("  (void)m;")
-    e("  join28_reduce(r, t);")
+    e("  join28(r, t);" if wide else "  join28_reduce(r, t);")
     e("}")
 
 
@@ -116,7 +122,8 @@ def main():
     e("// gfx950 Montgomery product on 14 x 28-bit limbs: product scanning with 64-bit accumulators")
     e("// in one inline-asm statement; split / join / conditional subtraction in C++ (fp_mul28.hpp).")
     e("// fp_mul28_gfx950_1acc: one accumulator (v[252:253]); fp_mul28_gfx950_2acc: two (v[250:253]),")
-    e("// see the generator for the issue order.")
+    e("// see the generator for the issue order. fp_mul28w_gfx950: the one-accumulator schedule on")
+    e("// unshifted operands with a plain join, r = a b 2^-392 < 1.0064 p (fp_mul28.hpp, the wide form).")
     e("#pragma once")
     e("#include <stdint.h>")
     e("#include \"fp_mul28.hpp\"")
@@ -126,6 +133,9 @@ def main():
         lines, clob = fn()
         n[name] = len(lines)
         emit_fn(e, name, lines, clob)
+    lines, clob = body_1acc()
+    n["fp_mul28w_gfx950"] = len(lines)
+    emit_fn(e, "fp_mul28w_gfx950", lines, clob, wide=True)
     e("// one-chain order by default: the two-accumulator order measured 1.5% slower in the vote kernel")
     e("// (profiles/r03g_ab_summary.txt) and 5% slower at 4 waves per SIMD (r03g fp_mul28 ubench)")
     e("#if defined(OVH_FPMUL28_2ACC)")

@@ -7,6 +7,9 @@
 // every partial product is one v_mad_u64_u32 into the accumulator with no v_addc for a third
 // word (the 12 x 32 form pays one v_addc per v_mad). R = 2^392; the operand a enters shifted left
 // by 8 bits, so the product is a b 2^-384 as before (the VM's Montgomery form is unchanged).
+// The wide form (fp_mul_wide: no shift, a b 2^-392, no conditional subtraction -- the vote pool's
+// radix) is timed beside them; its values differ by the radix, and tests/test_gpu_fp_wide.py
+// checks them exactly.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 
@@ -37,7 +40,8 @@ __global__ __launch_bounds__(64) void k_chain(uint32_t iters, uint32_t* out) {
   for (uint32_t i = 0; i < iters; ++i) {
     if (V == 0) fp_mul(x, x, y);
     else if (V == 1) fp_mul28_gfx950_1acc(x.v, x.v, y.v);
-    else fp_mul28_gfx950_2acc(x.v, x.v, y.v);
+    else if (V == 2) fp_mul28_gfx950_2acc(x.v, x.v, y.v);
+    else fp_mul_wide(x, x, y);
   }
   Fp c;
   vm_canon(c, x);
@@ -54,10 +58,10 @@ int main() {
   const uint32_t iters = 2048;
   static uint32_t h0[4096 * 64 * 12], h1[4096 * 64 * 12];
   for (int grid : {1024, 4096}) {
-    float t[3];
-    size_t bad[3] = {0, 0, 0};
-    for (int v = 0; v < 3; ++v) {
-      auto k = v == 0 ? k_chain<0> : v == 1 ? k_chain<1> : k_chain<2>;
+    float t[4];
+    size_t bad[4] = {0, 0, 0, 0};
+    for (int v = 0; v < 4; ++v) {
+      auto k = v == 0 ? k_chain<0> : v == 1 ? k_chain<1> : v == 2 ? k_chain<2> : k_chain<3>;
       uint32_t* d = v == 0 ? d0 : d1;
       hipLaunchKernelGGL(k, dim3(grid), dim3(64), 0, 0, iters, d);
       (void)hipDeviceSynchronize();
@@ -67,12 +71,14 @@ int main() {
       (void)hipEventSynchronize(b);
       (void)hipEventElapsedTime(&t[v], a, b);
       (void)hipMemcpy(v == 0 ? h0 : h1, d, grid * 64 * 48, hipMemcpyDeviceToHost);
-      if (v)
+      if (v == 1 || v == 2)
         for (size_t i = 0; i < (size_t)grid * 64 * 12; ++i) bad[v] += h0[i] != h1[i];
     }
     printf("{\"waves\": %d, \"ns_per_mul_32x12\": %.1f, \"ns_per_mul_28x14_1acc\": %.1f, \"ns_per_mul_28x14_2acc\": "
-           "%.1f, \"speedup_1acc\": %.3f, \"speedup_2acc\": %.3f, \"mismatched_words\": [%zu, %zu]}\n",
-           grid, t[0] * 1e6 / iters, t[1] * 1e6 / iters, t[2] * 1e6 / iters, t[0] / t[1], t[0] / t[2], bad[1], bad[2]);
+           "%.1f, \"ns_per_mul_28x14_wide\": %.1f, \"speedup_1acc\": %.3f, \"speedup_2acc\": %.3f, "
+           "\"speedup_wide_over_1acc\": %.3f, \"mismatched_words\": [%zu, %zu]}\n",
+           grid, t[0] * 1e6 / iters, t[1] * 1e6 / iters, t[2] * 1e6 / iters, t[3] * 1e6 / iters, t[0] / t[1], t[0] / t[2],
+           t[1] / t[3], bad[1], bad[2]);
   }
   return 0;
 }

@@ -2,7 +2,7 @@
 """VALU attribution of the vote program: where the pool kernel's VALU
 instructions per quad go, by interpreter path.
 
-    python tools/valu_attr.py [--inc consensus_overlord_amd/csrc/vm_progs.inc] [--build r06] [--md]
+    python tools/valu_attr.py [--inc consensus_overlord_amd/csrc/vm_progs.inc] [--build wide] [--prog VOTE] [--md]
 
 Two inputs:
   * how often each interpreter path runs: from the encoded vote program itself (vm_progs.inc
@@ -114,6 +114,20 @@ PATHS["shared"] = dict(PATHS["r06x"])
 PATHS["shared"]["loop: prefetch ring rotation + loop test"] = (0, "ring")
 PATHS["shared1"] = dict(PATHS["r06x"])
 PATHS["shared1"]["loop: prefetch ring rotation + loop test"] = (6, "ring")
+# wide: the pool's vote loop on radix-2^392 programs (fpvm.hpp run<.., 392>). Like every table
+# here its per-pass counts are hand-counted in the disassembly of k_vm_pool (llvm-objdump -d of the
+# gfx950 code object in libovhip.so); the tool reads no code object. From the last v_mad_u64_u32
+# of the product block to the H_FLAG branch the parent has 49 VALU (3 of the last column, 22 of
+# the join, 24 of the conditional subtraction: 12 v_sub(b)_co + 12 v_cndmask; the 26 of the older
+# tables is the r05 / r06 builds' count, which had two more moves) and this build 25: the
+# subtraction is gone from the product block. The flag block (H_FLAG branch to the result store)
+# grows from 55 to 68 in line: the test of the product against p (12 v_xor, the or-tree, one
+# compare, the flag's select). phase_counts charges that row to flag phases only, which it reads
+# from the program's WIDE bit (w3 bit 25 of a product phase's first lane)
+PATHS["wide"] = dict(PATHS["shared"])
+PATHS["wide"]["product: conditional subtraction"] = (13, "condsub")
+PATHS["wide"]["product: join 14x28 -> 12x32"] = (22, "join")
+W_WIDE = 1 << 25
 
 
 def load_prog(inc, name="VOTE"):
@@ -153,8 +167,11 @@ def phase_counts(w, nph, code, side):
             c["pre-add with 2p - x negations (H_MULNEG)" if hdr & H_MULNEG else "pre-add, unit signs"] += 1
             for k in ("product: v_mad_u64_u32", "product: split 12x32 -> 14x28", "product: Montgomery digits (mul_lo, and)",
                       "product: column shifts (lshrrev_b64) + moves", "product: join 14x28 -> 12x32",
-                      "product: conditional subtraction", "result store address"):
+                      "result store address"):
                 c[k] += 1
+            # a radix-392 phase subtracts only for its flag ops
+            if not lanes[0][3] & W_WIDE or hdr & H_FLAG:
+                c["product: conditional subtraction"] += 1
             if hdr & H_FLAG:
                 c["flag ops (sgn0 / eq / lex, H_FLAG)"] += 1
                 if OPC["lex"] in ops:
@@ -180,10 +197,11 @@ def phase_counts(w, nph, code, side):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--inc", default=os.path.join(ROOT, "consensus_overlord_amd", "csrc", "vm_progs.inc"))
-    ap.add_argument("--build", default="shared", choices=sorted(PATHS))
+    ap.add_argument("--build", default="wide", choices=sorted(PATHS))
+    ap.add_argument("--prog", default="VOTE", choices=["VOTE", "VOTE_T"])
     ap.add_argument("--md", action="store_true")
     a = ap.parse_args()
-    w, nph, code, side = load_prog(a.inc)
+    w, nph, code, side = load_prog(a.inc, a.prog)
     cnt = phase_counts(w, nph, code, side)
     cost = PATHS[a.build]
     rows = [(k, cnt[k], v, cls, cnt[k] * v) for k, (v, cls) in cost.items()]
