@@ -43,6 +43,8 @@ SIGNATURES = [
     ("ovh_msg_cache_stats", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
     ("ovh_prime_hashes", ctypes.c_int, [_vp, _sz, _u8p]),
     ("ovh_prime_stats", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
+    ("ovh_sig_cache_config", ctypes.c_int, [_vp, _sz]),
+    ("ovh_agg_stats", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
     ("ovh_samemsg_stats", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
     ("ovh_verify_qc_batch", ctypes.c_int, [_vp, _sz, _u8p, _u8p, _u8p, _sz, _vp]),
     ("ovh_build_qc", ctypes.c_int, [_vp, _sz, _u8p, _u8p, _sz, _u8p, _vp, _vp, _u8p, _u8p, _sz,

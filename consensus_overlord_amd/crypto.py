@@ -331,6 +331,24 @@ class ConsensusCrypto:
         raise_for(self.lib.ovh_prime_stats(self.ctx.ptr, st))
         return tuple(int(x) for x in st)
 
+    SIG_CACHE_DEFAULT = 4096   # include/ovhip.h OVH_SIG_CACHE_DEFAULT
+
+    def sig_cache_config(self, capacity: int) -> None:
+        """Capacity of the signature-point cache (ovh_sig_cache_config): the decompressed points
+        of signatures this context signed or verified with code 0, which aggregate_signatures
+        sums without decompressing them again. 0 disables and empties it; a new capacity empties
+        it; at most 65,536 entries."""
+        raise_for(self.lib.ovh_sig_cache_config(self.ctx.ptr, int(capacity)))
+
+    def agg_stats(self):
+        """(sigma entries registered, entries now, aggregate_signatures calls on the cache route,
+        ... on the full path, signatures of those not found in the cache,
+        verify_aggregated_signature calls on the table route, of those on a message-cache H,
+        ... on the full path) since the context was created (ovh_agg_stats)."""
+        st = (ctypes.c_uint64 * 8)()
+        raise_for(self.lib.ovh_agg_stats(self.ctx.ptr, st))
+        return tuple(int(x) for x in st)
+
     def cache_stats(self):
         """(hits, misses, entries) of the verdict cache."""
         st = (ctypes.c_uint64 * 3)()

@@ -53,6 +53,7 @@
 #include "proof.hpp"
 #include "qc_round_groups.hpp"
 #include "qc_segments.hpp"
+#include "sig_cache.hpp"
 #include "rlp.hpp"
 #include "sm3.hpp"
 #include "sm3_bulk.hpp"
@@ -895,7 +896,7 @@ __global__ __launch_bounds__(64) void k_vm_sigchk(uint32_t n, VmDev prog, const 
   const bool active = i < n;
   if (active && lane == 0) {
     uint32_t x1[12], x0[12], bad, inf, sort, xz;
-    parse_hdr(data + off[i], 96, x1, x0, bad, inf, sort, xz);
+    parse_hdr(data + (off ? off[i] : (uint64_t)96 * i), 96, x1, x0, bad, inf, sort, xz);  // off null: packed
     slot_put(slots, VM_SIGCHK_IN[VM_SIGCHK_IN_SIG_X1], x1);
     slot_put(slots, VM_SIGCHK_IN[VM_SIGCHK_IN_SIG_X0], x0);
     slot_flag(slots, VM_SIGCHK_IN[VM_SIGCHK_IN_SIG_SORT], sort);
@@ -1814,6 +1815,20 @@ struct ovh_ctx {
   // consumers of the cache beside the per-call verify (OVH_PRIME_SIGN / OVH_PRIME_BATCH, read
   // at ovh_create)
   bool prime_sign = true, prime_batch = true;
+  // signature-point cache (sc_* below the message table): the host index
+  // (sig_cache.hpp), the slab (S_SIG + 6 planes of sc.cap entries: the masked sum reads a sigma at
+  // plane S_SIG, as in a batch slot's state) and the capacity the next allocation takes; off in
+  // the sub-contexts of a multi-device context. qc_table: ovh_verify_aggregated's table route.
+  // Single votes (ovh_sign, the per-call verify) fill on prime_st, beside the call's own work:
+  // sc_ev is recorded behind the last such fill, sc_pending says that a reader has yet to wait
+  // for it (sc_touch). qc_table (OVH_QC_TABLE): 0 off, 1 for a hash in the message table, 2 always.
+  SigCache sc;
+  uint32_t* sc_planes = nullptr;
+  uint32_t sc_want = OVH_SIG_CACHE_DEFAULT;
+  hipEvent_t sc_ev = nullptr;
+  bool sc_pending = false;
+  int qc_table = 1;
+  uint64_t agg_route = 0, agg_old = 0, agg_miss = 0, vagg_route = 0, vagg_h = 0, vagg_old = 0;
   uint32_t clk_wgs = 0;    // OVH_FLAG_VM_CLOCK: workgroups of the last vote launch
   bool clk_table = false;  // ... and whether it was vote_t
   std::vector<uint32_t> blind_h;  // host copy of the last compression blinds (upload_blinds)
@@ -2674,6 +2689,154 @@ static void hc_register(ovh_ctx* c, uint32_t he, const std::string& hk) {
   c->hc_index[hk] = he;
 }
 
+// ---- the signature-point cache: the affine G2 point of signatures this
+// context returned from ovh_sign or verified with code 0, keyed by their exact 96 bytes on the host
+// (sig_cache.hpp), so that ovh_aggregate_sigs over such signatures sums cached points and neither
+// decompresses nor subgroup-checks them again. A batch's entries are one contiguous run of the
+// ring, filled by one launch: k_vm_sigchk without the subgroup check straight into the run, or --
+// behind a same-message batch, whose vote program left every sigma in the state slab --
+// k_sc_scatter. A batch's fill runs on c->stream or on the batch's final stream, both of which the
+// filling call synchronises before it returns; a single vote's fill (ovh_sign, the per-call
+// verify) runs on c->prime_st beside the call's own work and is not waited for by the host
+// (sc_fill_one). The one reader (ovh_aggregate_sigs) runs on c->stream and is synchronous.
+// Invariants (the message table's):
+//  - an entry is registered in the host index (sc_register) only after every launch that fills
+//    it was accepted and its vote's code 0 has arrived on the host; entries claimed for votes
+//    that turn out invalid stay unregistered, whatever the launch wrote there;
+//  - nothing reads an entry before its fill has completed on the device: a batch's fill was
+//    waited for by its call, and sc_touch makes the reader's stream wait for the last single
+//    fill (an event wait, as hc_touch);
+//  - nothing overwrites an entry that a kernel enqueued earlier may still read or write: the
+//    reader has synchronised before its call returned, single fills are in order on one stream,
+//    a batch's fill waits for the last single fill (sc_touch), and sc_claim drops the old keys
+//    before the launch;
+//  - a batch stages its votes table-first (table_split): entry e0 + j holds the point of staged
+//    vote j and is registered under the bytes of the caller's vote perm[j] (sc_fill_register).
+// The words behind the planes are the masked sum's `taken` array, one per entry, all nonzero;
+// behind them 32 words of staging for a single fill (the signature, sigchk's code word).
+static int sc_ensure(ovh_ctx* c) {
+  if (c->sc.cap == c->sc_want && (c->sc_planes || !c->sc_want)) return 0;
+  CHK(sync_all(c));
+  if (c->prime_st) HIPCHK(hipStreamSynchronize(c->prime_st));  // single fills in flight
+  c->sc_pending = false;
+  if (c->sc_planes) (void)hipFree(c->sc_planes);
+  c->sc_planes = nullptr;
+  sc_reset(c->sc, 0);
+  if (!c->sc_want) return 0;
+  const size_t pw = (size_t)(S_SIG + 6) * 12 * c->sc_want;
+  HIPCHK(hipMalloc(&c->sc_planes, (pw + c->sc_want + 32) * 4));
+  HIPCHK(hipMemsetAsync(c->sc_planes + pw, 1, (size_t)c->sc_want * 4, c->stream));
+  sc_reset(c->sc, c->sc_want);
+  return 0;
+}
+static const uint32_t* sc_taken(const ovh_ctx* c) { return c->sc_planes + (size_t)(S_SIG + 6) * 12 * c->sc.cap; }
+
+// sigma planes of staged vote q (state slab, affine) -> cache entry e0 + q, for the votes with
+// code 0 (k_copy_h for a run of entries): workgroup q.
+__global__ __launch_bounds__(64) void k_sc_scatter(uint32_t n, uint32_t e0, const int32_t* __restrict__ codes, Slab st,
+                                                   Slab sc) {
+  const uint32_t q = blockIdx.x;
+  if (q >= n || q >= st.cap || e0 >= sc.cap || q >= sc.cap - e0 || codes[q] != 0) return;
+  const uint32_t e = e0 + q;
+  for (uint32_t w = threadIdx.x; w < 4 * 12; w += 64)
+    sc.p[(size_t)(S_SIG * 12 + w) * sc.cap + e] = st.p[(size_t)(S_SIG * 12 + w) * st.cap + q];
+}
+
+// A fill in flight: entries [e0, e0 + n) stand for the call's staged votes [0, n).
+struct ScFill {
+  uint32_t e0 = SC_NONE, n = 0;
+};
+
+// Whether a call over these n signatures (host bytes, any order) should fill: the cache is on,
+// the run fits, and at least one signature is not in it yet.
+static bool sc_wants(ovh_ctx* c, size_t n, const uint8_t* sigs) {
+  if (!c->sc_want || n == 0 || n > c->sc_want) return false;
+  if (sc_ensure(c) != 0 || !c->sc.cap) return false;
+  uint32_t e;
+  for (size_t i = 0; i < n; ++i)
+    if (!sc_find(c->sc, sigs + 96 * i, &e)) return true;
+  return false;
+}
+
+// Before `st` reads or fills entries: it waits for the last single fill. reader: the wait need
+// not be repeated until the next single fill.
+static int sc_touch(ovh_ctx* c, hipStream_t st, bool reader) {
+  if (!c->sc_pending) return 0;
+  HIPCHK(hipStreamWaitEvent(st, c->sc_ev, 0));
+  if (reader) c->sc_pending = false;
+  return 0;
+}
+
+// Claims a run for n staged signatures (96 bytes each at d_sigs) and fills it on `st`: one sigchk
+// launch without the subgroup check (a registered signature's vote had code 0: it is in G2).
+// Call sc_wants first. No host synchronisation.
+static int sc_fill_sigchk(ovh_ctx* c, hipStream_t st, size_t n, const uint8_t* d_sigs, ScFill* f) {
+  CHK(ensure_scr(c, n));  // sigchk's code words: not read
+  CHK(sc_touch(c, st, false));
+  const uint32_t e0 = sc_claim(c->sc, (uint32_t)n);
+  if (e0 == SC_NONE) return 0;
+  constexpr uint32_t SL = 64 / VM_SIGCHK_W;
+  k_vm_sigchk<<<(uint32_t)((n + SL - 1) / SL), 64, LDS_SIGCHK, st>>>(
+      (uint32_t)n, c->vm_sigchk, c->vm_consts, d_sigs, nullptr, 0, c->scr_sig,
+      Slab{c->sc_planes + (size_t)S_SIG * 12 * c->sc.cap + e0, c->sc.cap});
+  HIPCHK(hipGetLastError());  // a failed launch leaves the run unregistered
+  f->e0 = e0;
+  f->n = (uint32_t)n;
+  return 0;
+}
+
+// The same behind a same-message batch on its final stream: the state slab's sigma of the votes
+// with code 0 (d_codes, staged order) copied into the run.
+static int sc_fill_scatter(ovh_ctx* c, hipStream_t st, size_t n, Slab state, const int32_t* d_codes, ScFill* f) {
+  CHK(sc_touch(c, st, false));
+  const uint32_t e0 = sc_claim(c->sc, (uint32_t)n);
+  if (e0 == SC_NONE) return 0;
+  k_sc_scatter<<<(uint32_t)n, 64, 0, st>>>((uint32_t)n, e0, d_codes, state, Slab{c->sc_planes, c->sc.cap});
+  HIPCHK(hipGetLastError());
+  f->e0 = e0;
+  f->n = (uint32_t)n;
+  return 0;
+}
+
+// One signature (host bytes) on c->prime_st, beside whatever the call runs on c->stream: the bytes
+// travel as a kernel argument (as a prime's hashes), so nothing is copied from pageable memory
+// and the call's staging buffer is not read; sigchk (1.1 ms on its one slice) then hides behind
+// the vote's own check. Not waited for by the host: sc_ev orders later users behind it.
+struct Sig96 {
+  uint32_t w[24];
+};
+__global__ __launch_bounds__(64) void k_sc_put(Sig96 s, uint32_t* __restrict__ dst) {
+  if (threadIdx.x < 24) dst[threadIdx.x] = s.w[threadIdx.x];
+}
+static int sc_fill_one(ovh_ctx* c, const uint8_t* sig, ScFill* f) {
+  if (!c->prime_st) HIPCHK(stream_new(&c->prime_st, 0));
+  if (!c->sc_ev) HIPCHK(hipEventCreateWithFlags(&c->sc_ev, hipEventDisableTiming));
+  const uint32_t e0 = sc_claim(c->sc, 1);
+  if (e0 == SC_NONE) return 0;
+  Sig96 s;
+  memcpy(s.w, sig, 96);
+  uint32_t* stage = c->sc_planes + (size_t)(S_SIG + 6) * 12 * c->sc.cap + c->sc.cap;
+  const hipStream_t ps = c->prime_st;
+  k_sc_put<<<1, 64, 0, ps>>>(s, stage);
+  k_vm_sigchk<<<1, 64, LDS_SIGCHK, ps>>>(1, c->vm_sigchk, c->vm_consts, (const uint8_t*)stage, nullptr, 0,
+                                         (int32_t*)(stage + 24), Slab{c->sc_planes + (size_t)S_SIG * 12 * c->sc.cap + e0, c->sc.cap});
+  HIPCHK(hipGetLastError());  // a failed launch leaves the entry unregistered
+  HIPCHK(hipEventRecord(c->sc_ev, ps));
+  c->sc_pending = true;
+  f->e0 = e0;
+  f->n = 1;
+  return 0;
+}
+
+// Once the codes are on the host: staged vote j (the caller's vote perm[j]; perm null: j) with
+// code 0 is registered under the caller's bytes of that vote.
+static void sc_fill_register(ovh_ctx* c, const ScFill& f, const uint8_t* sigs, const uint32_t* perm,
+                             const int32_t* staged_codes) {
+  if (f.e0 == SC_NONE) return;
+  for (uint32_t j = 0; j < f.n; ++j)
+    if (staged_codes[j] == 0) sc_register(c->sc, f.e0 + j, sigs + 96 * (size_t)(perm ? perm[j] : j));
+}
+
 // ovh_prime_hashes on one device (caller holds c->mu): hash_to_field and hash_to_G2 (k_vm_h2g,
 // four hashes per wave) of the hashes not in the table into the prime slab on c->prime_st, at
 // once; then, behind everything enqueued on c->stream so far (earlier readers of the entries
@@ -2725,8 +2888,12 @@ static int prime_locked(ovh_ctx* c, size_t k, const uint8_t* hashes) {
 // same hash): a hash in the table (seen before, or primed) runs vote1h / vote_t1h on its H,
 // without hash_to_G2 (vote1 2,061 -> 1,444 phases); a new one runs vote1 / vote_t1, whose stored
 // H is copied into the table. Null: no table.
+// h_lookup (ovh_verify_aggregated's table route): the table is only looked up -- a hash that is
+// not there runs vote1 / vote_t1 and is not entered, and neither counter moves; *h_hit: whether
+// the vote ran on a table entry.
 static int verify_one_locked(ovh_ctx* c, const uint8_t* d_sig, const uint8_t* d_hash, KeySrc key, int32_t* d_code,
-                             const uint8_t* h_host = nullptr) {
+                             const uint8_t* h_host = nullptr, bool h_lookup = false, bool* h_hit = nullptr) {
+  if (h_lookup && !c->hc_planes) h_host = nullptr;
   CHK(ensure_cap(c, 1));
   int slot;
   CHK(take_slot(c, &slot));
@@ -2740,7 +2907,8 @@ static int verify_one_locked(ovh_ctx* c, const uint8_t* d_sig, const uint8_t* d_
     hk.assign((const char*)h_host, 32);
     uint32_t he;
     if (hc_find(c, hk, &he)) {
-      ++c->hc_hits;
+      if (!h_lookup) ++c->hc_hits;
+      if (h_hit) *h_hit = true;
       CHK(hc_touch(c));
       if (key.bytes)
         k_vm_vote1h<false><<<1, 64, LDS_VOTE1H, st>>>(c->vm_vote1h, c->vm_consts, key.bytes, PkSrc{}, d_sig, s, d_code,
@@ -2754,7 +2922,8 @@ static int verify_one_locked(ovh_ctx* c, const uint8_t* d_sig, const uint8_t* d_
       HIPCHK(hipGetLastError());
       return 0;
     }
-    ++c->hc_misses;
+    if (h_lookup) h_host = nullptr;
+    else ++c->hc_misses;
   }
   uint32_t he = 0;
   if (h_host) {  // the entry is filled in stream order, before any later call can read it
@@ -3236,6 +3405,10 @@ static int verify_host_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const u
     samemsg_plan(n, hashes, perm, pl);
     same = 2 * (size_t)pl.G <= n;
   }
+  // the signature-point cache is filled by one vote, by the small route's sizes and by the
+  // same-message route; the pool route keeps no sigma and fills nothing
+  const bool fill = (same || n <= c->small_max || n == 1) && sc_wants(c, n, sigs);
+  ScFill scf;
   pl.off = (n * (96 + 32 + 48 + 4 + 4) + 255) / 256 * 256;
   // (behind the table indices: the message-table entries of a part on primed hashes)
   CHK(ensure_in(c, same ? pl.off + pl.bytes + 64 : n * (96 + 32 + 48 + 4 + 4 + 4) + 64));
@@ -3259,21 +3432,30 @@ static int verify_host_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const u
     int slot;
     CHK(take_slot(c, &slot));
     CHK(verify_samemsg_locked(c, slot, n, d, t, (const int32_t*)(d + n * 180), d + n * 128 + 48 * t, pd, dc));
+    // the vote program left every sigma in the slot's state: behind the bisection, the votes
+    // with code 0 are copied into their entries (waited for by sync_all below)
+    if (fill) CHK(sc_fill_scatter(c, c->fs[slot], n, Slab{c->state_slot[slot], c->cap}, dc, &scf));
   } else if (n == 1) {
+    if (fill) CHK(sc_fill_one(c, sigs, &scf));  // on the side stream, beside the check
     CHK(verify_one_locked(c, d, d + 96, staged_key(c, n, d, t, 0), dc, hashes));
   } else {
     CHK(verify_parts_locked(c, n, d, t, perm, hashes, dc, (uint32_t*)(d + n * 184), hent));
+    // sigma of every staged vote from one sigchk launch, on the main stream behind the vote
+    // kernels and beside the final streams' fold and final exponentiation
+    if (fill && n <= c->small_max) CHK(sc_fill_sigchk(c, c->stream, n, d, &scf));
   }
   CHK(sync_all(c));
+  std::vector<int32_t> pc;
   if (perm.empty()) {
     HIPCHK(hipMemcpyAsync(codes, dc, 4 * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   } else {
-    std::vector<int32_t> pc(n);
+    pc.resize(n);
     HIPCHK(hipMemcpyAsync(pc.data(), dc, 4 * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     for (size_t j = 0; j < n; ++j) codes[perm[j]] = pc[j];
   }
+  sc_fill_register(c, scf, sigs, perm.empty() ? nullptr : perm.data(), perm.empty() ? codes : pc.data());
   return 0;
 }
 
@@ -3691,6 +3873,11 @@ ovh_ctx* ovh_create(int device, const uint8_t* dst, size_t dst_len, uint32_t fla
   if (const char* e = getenv("OVH_SAMEMSG")) c->samemsg = atoi(e);
   if (const char* e = getenv("OVH_PRIME_SIGN")) c->prime_sign = atoi(e) != 0;
   if (const char* e = getenv("OVH_PRIME_BATCH")) c->prime_batch = atoi(e) != 0;
+  if (const char* e = getenv("OVH_SIG_CACHE")) {
+    const long v = atol(e);
+    c->sc_want = v <= 0 ? 0u : v > OVH_SIG_CACHE_MAX ? (uint32_t)OVH_SIG_CACHE_MAX : (uint32_t)v;
+  }
+  if (const char* e = getenv("OVH_QC_TABLE")) c->qc_table = atoi(e) <= 0 ? 0 : atoi(e) == 1 ? 1 : 2;
   if (const char* e = getenv("OVH_SHARD_SPAN")) c->shard_span = (uint32_t)atoi(e);
   if (const char* e = getenv("OVH_SHARD_STREAMS")) c->shard_streams = atoi(e) == 3 ? 3u : 2u;
   if (const char* e = getenv("OVH_NFIN")) c->nfin = atoi(e) == 3 ? 3u : atoi(e) == 2 ? 2u : NFIN_STREAMS;
@@ -3789,6 +3976,7 @@ ovh_ctx* ovh_create_multi(const int* devices, int ndev, const uint8_t* dst, size
       ovh_destroy(root);
       return nullptr;
     }
+    s->sc_want = 0;  // no signature-point cache on the devices of a multi context
     root->sub.push_back(s);
   }
   // Peer access (xGMI) for every ordered pair of distinct devices: the partials go from every
@@ -3842,7 +4030,7 @@ static void destroy_one(ovh_ctx* c) {
   (void)hipSetDevice(c->device);
   each_stream(c, [](hipStream_t s) { (void)hipStreamSynchronize(s); });
   if (c->prime_slab) (void)hipFree(c->prime_slab);
-  for (hipEvent_t e : {c->prime_ev0, c->prime_ev})
+  for (hipEvent_t e : {c->prime_ev0, c->prime_ev, c->sc_ev})
     if (e) (void)hipEventDestroy(e);
   for (int k = 0; k < OVH_BATCH_SLOTS; ++k)
     for (void* p : {(void*)c->grp_ok[k], (void*)c->msm_buf[k], (void*)c->gslab[k]})
@@ -3853,7 +4041,7 @@ static void destroy_one(ovh_ctx* c) {
                   (void*)c->pool_scr, (void*)c->plog, (void*)c->vm_consts,
                   (void*)c->fin, (void*)c->scr, (void*)c->scr_pk, (void*)c->scr_sig, (void*)c->comb,
                   (void*)c->tab.planes, (void*)c->tab.flags, (void*)c->tab.qc, (void*)c->tab.qcg, (void*)c->qc_buf, (void*)c->qt_buf, (void*)c->hc_planes, (void*)c->hc_inf, (void*)c->gather,
-                  (void*)c->mfin, (void*)c->sm1_plan, (void*)c->sm1_hash, (void*)c->rsig})
+                  (void*)c->mfin, (void*)c->sm1_plan, (void*)c->sm1_hash, (void*)c->rsig, (void*)c->sc_planes})
     if (p) (void)hipFree(p);
   for (void* p : c->vm_bufs) (void)hipFree(p);
   for (const QcRound& r : c->rounds) (void)hipFree(r.dev);
@@ -4173,6 +4361,14 @@ int ovh_sign(ovh_ctx* c, const uint8_t* key, size_t key_len, const uint8_t* hash
   HIPCHK(hipMemsetAsync(c->in_buf, 0, 32, c->stream));
   HIPCHK(hipMemcpyAsync(out, c->in_buf + 64, 96, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
+  // the leader's own vote never comes back through a verify: its sigma goes into the
+  // signature-point cache here, behind the return (a signature of this context is in G2)
+  if (sc_wants(c, 1, out)) {
+    ScFill f;
+    const int32_t ok = 0;
+    CHK(sc_fill_one(c, out, &f));
+    sc_fill_register(c, f, out, nullptr, &ok);
+  }
   return 0;
 }
 
@@ -4219,10 +4415,15 @@ int ovh_verify(ovh_ctx* c, const uint8_t* sig, size_t sig_len, const uint8_t* ha
     std::vector<uint32_t> perm;
     CHK(stage_split(s, 1, sig, hash, pk, &d, &t, perm));
     int32_t* dc = (int32_t*)(d + 176);
+    // the vote's sigma into the signature-point cache, on the side stream beside the check
+    // (as verify_host_locked); registered below when the vote turns out valid
+    ScFill scf;
+    if (sc_wants(s, 1, sig)) CHK(sc_fill_one(s, sig, &scf));
     CHK(verify_one_locked(s, d, d + 96, staged_key(s, 1, d, t, 0), dc, hash));
     int32_t out = -1;
     HIPCHK(hipMemcpyAsync(&out, dc, 4, hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
+    sc_fill_register(s, scf, sig, nullptr, &out);
     return out;
   }
   // other encodings (uncompressed keys / signatures, other lengths): k_canon_one turns them into
@@ -4276,6 +4477,61 @@ static size_t list_bytes(const size_t* lens, size_t n) {
   return t;
 }
 
+// ovh_aggregate_sigs on the signature-point cache. Taken only when the
+// cache is on (a single-device context), n >= 1, every signature has 96 and every key 48 bytes,
+// every voter is a validator-table entry with clean host flags (parsed, in G1) and every
+// signature is in the cache; returns 1 otherwise, and the caller runs the full path from its
+// start. Every condition implies what that path checks -- a cached signature decodes and is in
+// G2, a clean table key parses -- so it would return 0 and the compression of the same sum.
+// The entries (4 n bytes in place of the 144 n of signatures and keys) go up as a one-group
+// segment list padded with QC_NONE to whole chunks; the list-indexed masked sum (k_qc_chunk<true>,
+// k_qc_upper<true>) reads each sigma from the cache slab, a signature listed twice twice; one
+// compression, one copy, one host synchronisation.
+static int aggregate_cached_locked(ovh_ctx* c, const uint8_t* sigs, const size_t* sig_lens, const uint8_t* pks,
+                                   const size_t* pk_lens, size_t n, uint8_t out[96]) {
+  if (!c->sc_want || n == 0 || n > (1u << 20) || !c->tab.n) return 1;
+  for (size_t i = 0; i < n; ++i)
+    if (sig_lens[i] != 96 || pk_lens[i] != 48) return 1;
+  CHK(sc_ensure(c));
+  if (!c->sc.cap) return 1;
+  const size_t chunks = (n + MSM_CH - 1) >> MSM_CH_LV;
+  std::vector<uint32_t> list(chunks * MSM_CH + 2, QC_NONE);  // the entries, pads, then the segment (0, chunks)
+  size_t miss = 0;
+  for (size_t i = 0; i < n; ++i)
+    if (!sc_find(c->sc, sigs + 96 * i, &list[i])) ++miss;
+  if (miss) {
+    c->agg_miss += miss;
+    return 1;
+  }
+  std::string k(48, '\0');
+  for (size_t i = 0; i < n; ++i) {
+    memcpy(&k[0], pks + 48 * i, 48);
+    auto it = c->tab.index.find(k);
+    if (it == c->tab.index.end() || (c->tab.hflags[it->second] & (PKF_PARSE | PKF_GRP))) return 1;
+  }
+  list[chunks * MSM_CH] = 0;
+  list[chunks * MSM_CH + 1] = (uint32_t)chunks;
+  CHK(ensure_scr(c, chunks * (MSM_CH / 2)));  // the sum's tree: 32 entries per chunk
+  CHK(ensure_in(c, list.size() * 4 + 96 + 64));
+  uint32_t* dlist = (uint32_t*)c->in_buf;
+  uint32_t* dseg = dlist + chunks * MSM_CH;
+  uint8_t* d96 = (uint8_t*)(dseg + 2);
+  CHK(sc_touch(c, c->stream, true));
+  HIPCHK(hipMemcpyAsync(dlist, list.data(), list.size() * 4, hipMemcpyHostToDevice, c->stream));
+  MsmArgs a{};
+  a.st = Slab{c->sc_planes, c->sc.cap};
+  a.A = Slab{c->scr, c->scr_cap};
+  k_qc_chunk<true><<<(uint32_t)chunks, 64, LDS_MSM8, c->stream>>>((uint32_t)n, sc_taken(c), dlist, c->vm_madd, c->vm_padd,
+                                                               MSM8_STRIDE_W, c->vm_consts, a);
+  if (chunks > 1) k_qc_upper<true><<<1, 64, LDS_MSM8, c->stream>>>(0, dseg, c->vm_padd, MSM8_STRIDE_W, c->vm_consts, a);
+  k_g2p_compress<<<1, 64, 0, c->stream>>>(a.A, d96);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, d96, 96, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  ++c->agg_route;
+  return 0;
+}
+
 int ovh_aggregate_sigs(ovh_ctx* c, const uint8_t* sigs, const size_t* sig_lens, size_t n_sigs, const uint8_t* pks,
                        const size_t* pk_lens, size_t n_pks, uint8_t out[96]) {
   if (!c || !out) return OVH_ERR_ARG;
@@ -4285,6 +4541,11 @@ int ovh_aggregate_sigs(ovh_ctx* c, const uint8_t* sigs, const size_t* sig_lens, 
   c = pick_sub(c);
   std::lock_guard<std::mutex> g(c->mu);
   HIPCHK(hipSetDevice(c->device));
+  if (n && sigs && pks) {
+    const int r = aggregate_cached_locked(c, sigs, sig_lens, pks, pk_lens, n, out);
+    if (r != 1) return r;
+  }
+  ++c->agg_old;
   // the signatures go through the VM (k_vm_sigchk + a padd tree, planes [0, 2n) of scr); a list
   // with other encodings (uncompressed, other lengths) is re-encoded first (k_canon_sig_list:
   // every item as 96 compressed bytes that parse to the same point or fail with the same code)
@@ -4616,6 +4877,70 @@ static int verify_aggregated_locked(ovh_ctx* c, const uint8_t* agg_sig, size_t a
   return r;
 }
 
+// ovh_verify_aggregated on the validator table. Taken when the signature
+// has 96 bytes, the hash 32, n >= 1, every key 48 bytes and every voter is found in the table;
+// returns 1 otherwise (and for a voter whose entry carries the group flag: the sum's own group
+// check decides, on the full path). A voter whose entry carries the parse flag: 102, as the full
+// path, which parses every key first. Else the entry list goes up (any order, duplicates allowed:
+// a list, not a bitmap), k_qc_apk sums the entries' points and the per-call check runs on the
+// aggregated key -- ovh_verify_qc_batch's path for one QC, whose codes equal this call's by that
+// entry point's contract. The hash is looked up in the message table and never entered: on a hit
+// vote_t1h runs on the table's H, without hash_to_G2. No key bytes go up, no key is decompressed;
+// one host synchronisation. OVH_QC_TABLE: 1 (the default) takes the route only on such a hit --
+// on a miss the full path, which runs hash_to_G2 beside the key work, is no slower (DESIGN.md
+// section 3.10) --, 2 on every hash, 0 never.
+static int verify_aggregated_table(ovh_ctx* c, const uint8_t* agg_sig, size_t agg_len, const uint8_t* hash,
+                                   size_t hash_len, const uint8_t* pks, const size_t* pk_lens, size_t n, int* code) {
+  const ValidatorTable& t = c->tab;
+  if (agg_len != 96 || !hash || hash_len != 32 || n == 0 || n > (1u << 24) || !t.n) return 1;
+  for (size_t i = 0; i < n; ++i)
+    if (pk_lens[i] != 48) return 1;
+  std::vector<uint32_t> ent(n + 2);  // the CSR offsets (0, n), then the entries
+  ent[0] = 0;
+  ent[1] = (uint32_t)n;
+  uint32_t fl = 0;
+  std::string k(48, '\0');
+  for (size_t i = 0; i < n; ++i) {
+    memcpy(&k[0], pks + 48 * i, 48);
+    auto it = t.index.find(k);
+    if (it == t.index.end()) return 1;
+    ent[2 + i] = it->second;
+    fl |= t.hflags[it->second];
+  }
+  if (fl & PKF_PARSE) {
+    ++c->vagg_route;
+    *code = OVH_ERR_PUBKEY;
+    return 0;
+  }
+  if (fl & PKF_GRP) return 1;
+  if (c->qc_table == 1) {  // the default: only on a hash whose H is in the message table
+    uint32_t he;
+    if (!c->hc_planes || !hc_find(c, std::string((const char*)hash, 32), &he)) return 1;
+  }
+  CHK(ensure_qc_buf(c, 1));
+  CHK(ensure_in(c, 256 + 4 * (n + 2) + 64));
+  uint8_t* d = c->in_buf;  // sig | hash | code | offsets, entries
+  int32_t* dc = (int32_t*)(d + 128);
+  uint32_t* doff = (uint32_t*)(d + 256);
+  HIPCHK(hipMemcpyAsync(d, agg_sig, 96, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(d + 96, hash, 32, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(doff, ent.data(), 4 * (n + 2), hipMemcpyHostToDevice, c->stream));
+  uint32_t* qflags = c->qc_buf + (size_t)3 * 12 * c->qc_cap;
+  k_qc_apk<<<1, 64, 0, c->stream>>>(1, doff, doff + 2, Slab{t.planes, t.cap}, Slab{c->qc_buf, c->qc_cap}, qflags);
+  HIPCHK(hipGetLastError());
+  bool hit = false;
+  const int e = verify_one_locked(c, d, d + 96, KeySrc{nullptr, PkSrc{c->qc_buf, c->qc_cap, qflags, nullptr}}, dc, hash,
+                                  true, &hit);
+  int32_t r = -1;
+  if (!e) (void)hipMemcpyAsync(&r, dc, 4, hipMemcpyDeviceToHost, c->stream);
+  HIPCHK(hipStreamSynchronize(c->stream));  // (also on an error: ent is the source of a copy)
+  CHK(e);
+  ++c->vagg_route;
+  c->vagg_h += hit;
+  *code = r;
+  return 0;
+}
+
 int ovh_verify_aggregated(ovh_ctx* c, const uint8_t* agg_sig, size_t agg_len, const uint8_t* hash, size_t hash_len,
                           const uint8_t* pks, const size_t* pk_lens, size_t n) {
   if (!c) return OVH_ERR_ARG;
@@ -4623,6 +4948,13 @@ int ovh_verify_aggregated(ovh_ctx* c, const uint8_t* agg_sig, size_t agg_len, co
   if (n && !pk_lens) return OVH_ERR_ARG;
   c = pick_sub(c);
   std::lock_guard<std::mutex> g(c->mu);
+  if (c->qc_table && pks) {
+    HIPCHK(hipSetDevice(c->device));
+    int code = 0;
+    const int r = verify_aggregated_table(c, agg_sig, agg_len, hash, hash_len, pks, pk_lens, n, &code);
+    if (r != 1) return r ? r : code;
+  }
+  ++c->vagg_old;
   return verify_aggregated_locked(c, agg_sig, agg_len, hash, hash_len, pks, pk_lens, n);
 }
 
@@ -4778,6 +5110,32 @@ int ovh_prime_stats(ovh_ctx* c, uint64_t stats[4]) {
     stats[1] += s->prime_skip;
     stats[2] += s->prime_signs;
     stats[3] += s->prime_parts;
+  }
+  return 0;
+}
+
+int ovh_sig_cache_config(ovh_ctx* c, size_t capacity) {
+  if (!c || capacity > OVH_SIG_CACHE_MAX) return OVH_ERR_ARG;
+  if (!c->sub.empty()) return 0;  // a multi-device context keeps no signature-point cache
+  std::lock_guard<std::mutex> g(c->mu);
+  HIPCHK(hipSetDevice(c->device));
+  c->sc_want = (uint32_t)capacity;
+  return sc_ensure(c);  // a new capacity (0 included) empties the cache; the same one keeps it
+}
+
+int ovh_agg_stats(ovh_ctx* c, uint64_t stats[8]) {
+  if (!c || !stats) return OVH_ERR_ARG;
+  for (int k = 0; k < 8; ++k) stats[k] = 0;
+  for (ovh_ctx* s : devices_of(c)) {
+    std::lock_guard<std::mutex> g(s->mu);
+    stats[0] += s->sc.registered;
+    stats[1] += sc_entries(s->sc);
+    stats[2] += s->agg_route;
+    stats[3] += s->agg_old;
+    stats[4] += s->agg_miss;
+    stats[5] += s->vagg_route;
+    stats[6] += s->vagg_h;
+    stats[7] += s->vagg_old;
   }
   return 0;
 }
@@ -5412,6 +5770,10 @@ static int build_qc_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint
   sel.taken = dtaken;
   enqueue_qc_select(st, tb.n, N, (uint32_t)t, sel, !rd);
   if (side) HIPCHK(hipStreamWaitEvent(st, c->ev_x[3], 0));
+  // the signature-point cache: a.st holds every staged vote's sigma (the slot's state, or the
+  // side slab), the votes with code 0 are copied into their entries
+  ScFill scf;
+  if ((side || n >= 2) && sc_wants(c, n, sigs)) CHK(sc_fill_scatter(c, st, n, a.st, dc, &scf));
   if (mo) {
     const uint32_t* dlist = (const uint32_t*)(d + pl.off + pl.bytes);
     enqueue_qc_sum(c, st, a, N, dtaken, &sg, dlist, dlist + sg.list.size(), d + ooff);
@@ -5444,6 +5806,7 @@ static int build_qc_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint
   HIPCHK(hipStreamSynchronize(st));
   drain.armed = false;
   CHK(pool_failed(c));
+  sc_fill_register(c, scf, sigs, perm.empty() ? nullptr : perm.data(), pc.data());
   for (size_t j = 0; j < n; ++j) {
     const size_t i = perm.empty() ? j : perm[j];
     codes[i] = pc[j];
@@ -5768,6 +6131,9 @@ static int rounds_add_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const ui
   CHK(enqueue_qc_rounds(c, st, a, N, (uint32_t)t, sel, drefs, sg, dlist, dseg, gw, drows, rc.out_sigs ? d + ooff : nullptr,
                         small ? c->ev_x[3] : nullptr));
   HIPCHK(hipGetLastError());
+  // the signature-point cache, as build_qc_locked: behind the sums (and the side slab's event)
+  ScFill scf;
+  if (sc_wants(c, n, sigs)) CHK(sc_fill_scatter(c, st, n, a.st, dc, &scf));
   drain.s[1] = st;
   HIPCHK(hipMemcpyAsync(pc.data(), dc, 4 * n, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(ptk.data(), dtaken, 4 * n, hipMemcpyDeviceToHost, st));
@@ -5776,6 +6142,7 @@ static int rounds_add_locked(ovh_ctx* c, size_t n, const uint8_t* sigs, const ui
   HIPCHK(hipStreamSynchronize(st));
   drain.armed = false;
   CHK(pool_failed(c));
+  sc_fill_register(c, scf, sigs, perm.empty() ? nullptr : perm.data(), pc.data());
   for (size_t j = 0; j < n; ++j) {
     const size_t i = perm.empty() ? j : perm[j];
     codes[i] = pc[j];

@@ -141,14 +141,33 @@ int ovh_sk_to_pk(ovh_ctx* ctx, const uint8_t* key, size_t key_len, uint8_t out[4
 int ovh_verify(ovh_ctx* ctx, const uint8_t* sig, size_t sig_len, const uint8_t* hash, size_t hash_len,
                const uint8_t* pk, size_t pk_len);
 
-/* Crypto::aggregate_signatures (consensus.rs:418-444): 96-byte compressed sum. */
+/* Crypto::aggregate_signatures (consensus.rs:418-444): 96-byte compressed sum.
+ *
+ * The route does not change what the call returns. On a single-device context with the
+ * signature-point cache on (ovh_sig_cache_config), a call with n >= 1 in which every signature
+ * has 96 and every key 48 bytes, every voter is a validator-table entry (ovh_set_validators)
+ * whose key parsed and lies in G1, and every signature is in the cache sums the cached points: it
+ * uploads 4 n bytes, decompresses and subgroup-checks nothing and waits for the device once. Any
+ * other call runs the full path from its start (there is no partial mode). */
 int ovh_aggregate_sigs(ovh_ctx* ctx, const uint8_t* sigs, const size_t* sig_lens, size_t n_sigs,
                        const uint8_t* pks, const size_t* pk_lens, size_t n_pks, uint8_t out[96]);
 
 /* BlsPublicKey::aggregate (consensus.rs:371): 48-byte compressed sum. */
 int ovh_aggregate_pks(ovh_ctx* ctx, const uint8_t* pks, const size_t* pk_lens, size_t n, uint8_t out[48]);
 
-/* Crypto::verify_aggregated_signature (consensus.rs:446-462, 365-382). */
+/* Crypto::verify_aggregated_signature (consensus.rs:446-462, 365-382).
+ *
+ * The route does not change what the call returns. With a 96-byte signature, a 32-byte hash,
+ * n >= 1, every key of 48 bytes and every voter found in the validator table, the call sums the
+ * table's points of the voters (any order, duplicates counted) and runs the per-call check on
+ * that key, as ovh_verify_qc_batch does for one QC: no key bytes go up and no key is decompressed
+ * (an entry whose key did not parse answers 102; one whose key lies outside G1 sends the call to
+ * the full path, where the sum's own group check decides). The hash is looked up in the message
+ * cache (ovh_prime_hashes) and never entered: on a hit the check runs without hash_to_G2, and
+ * ovh_msg_cache_stats does not move either way. The environment variable OVH_QC_TABLE (read at
+ * ovh_create) selects 0 = never, 1 = only for a hash that is in the message cache (default: on
+ * a hash that is not, the full path is as fast), 2 = for every hash. A
+ * multi-device context takes the route on the device the call lands on. */
 int ovh_verify_aggregated(ovh_ctx* ctx, const uint8_t* agg_sig, size_t agg_len, const uint8_t* hash, size_t hash_len,
                           const uint8_t* pks, const size_t* pk_lens, size_t n);
 
@@ -216,6 +235,33 @@ int ovh_prime_hashes(ovh_ctx* ctx, size_t k, const uint8_t* hashes /* k x 32 */)
  * repeated), stats[2] = ovh_sign calls served from the cache, stats[3] = small-batch parts run on
  * cached H; since ovh_create, summed over a multi-device context's devices. */
 int ovh_prime_stats(ovh_ctx* ctx, uint64_t stats[4]);
+
+/* The signature-point cache: per single-device context, the decompressed
+ * affine G2 point of fixed-size signatures that this context returned from ovh_sign or verified
+ * with code 0 (the fill never adds a host synchronisation; a single vote's runs on a side stream
+ * beside the check) -- by ovh_verify on the device, by ovh_verify_batch / ovh_prefetch of one vote, of
+ * 2 .. OVH_SMALL_MAX votes or on the same-message route, by ovh_build_qc / ovh_build_qcs, and by
+ * ovh_round_add / ovh_rounds_add -- keyed by the exact 96 signature bytes, FIFO replacement. The
+ * device-pointer, pipelined, asynchronous and sharded entry points, multi-device contexts and
+ * aggregated signatures fill nothing. ovh_aggregate_sigs reads it (see there); nothing else
+ * does, and ovh_set_validators leaves it alone (a signature's point does not depend on the
+ * table). `capacity` entries of 480 bytes; 0 disables the cache and empties it, a new capacity
+ * empties it, the current one keeps it. The environment variable OVH_SIG_CACHE (read at
+ * ovh_create) sets the initial capacity; the default is OVH_SIG_CACHE_DEFAULT, four full vote sets
+ * of a 1,024-validator table. Returns OVH_ERR_ARG for a NULL context or a capacity above
+ * OVH_SIG_CACHE_MAX (nothing changes); 0 on a multi-device context, which keeps no cache. */
+#define OVH_SIG_CACHE_DEFAULT 4096
+#define OVH_SIG_CACHE_MAX 65536
+int ovh_sig_cache_config(ovh_ctx* ctx, size_t capacity);
+/* Counters since ovh_create, summed over a multi-device context's devices:
+ *   stats[0] signature points registered in the cache   stats[1] entries now
+ *   stats[2] ovh_aggregate_sigs calls on the cache route stats[3] ... on the full path
+ *   stats[4] signatures of fixed-size full-path calls that were not found in the cache
+ *   stats[5] ovh_verify_aggregated calls on the table route
+ *   stats[6] of those, calls whose hash was in the message cache
+ *   stats[7] ovh_verify_aggregated calls on the full path
+ * Returns OVH_ERR_ARG for a NULL context or NULL stats (nothing is written). */
+int ovh_agg_stats(ovh_ctx* ctx, uint64_t stats[8]);
 
 /* Batched QC verification for block sync (check_block, consensus.rs:143-207): QC j = aggregated
  * signature sigs[j] (96 B) over hashes[j] (32 B, the SM3 of rlp(Vote{h, r, Precommit, block})),

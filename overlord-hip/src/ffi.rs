@@ -38,6 +38,8 @@ pub const OVH_PARTIAL_BYTES: usize = 864;
 pub const OVH_BATCH_SLOTS: usize = 6;
 pub const OVH_QC_GROUPS_MAX: usize = 64;
 pub const OVH_PRIME_MAX: usize = 64;
+pub const OVH_SIG_CACHE_DEFAULT: usize = 4096;
+pub const OVH_SIG_CACHE_MAX: usize = 65536;
 pub const OVH_ROUNDS_MAX: usize = 16;
 pub const OVH_ROUND_VOTES_MAX: usize = 1 << 24;
 
@@ -70,6 +72,8 @@ extern "C" {
     pub fn ovh_msg_cache_stats(ctx: *mut OvhCtx, stats: *mut u64) -> i32;
     pub fn ovh_prime_hashes(ctx: *mut OvhCtx, k: usize, hashes: *const u8) -> i32;
     pub fn ovh_prime_stats(ctx: *mut OvhCtx, stats: *mut u64) -> i32;
+    pub fn ovh_sig_cache_config(ctx: *mut OvhCtx, capacity: usize) -> i32;
+    pub fn ovh_agg_stats(ctx: *mut OvhCtx, stats: *mut u64) -> i32;
     pub fn ovh_verify_qc_batch(ctx: *mut OvhCtx, nq: usize, sigs: *const u8, hashes: *const u8, bitmaps: *const u8, bitmap_len: usize, codes: *mut i32) -> i32;
     pub fn ovh_build_qc(ctx: *mut OvhCtx, n: usize, sigs: *const u8, hash: *const u8, hash_len: usize, pks: *const u8, codes: *mut i32, taken: *mut u8, out_sig: *mut u8, bitmap: *mut u8, bitmap_len: usize, n_signed: *mut u32) -> i32;
     pub fn ovh_build_qcs(ctx: *mut OvhCtx, n: usize, sigs: *const u8, hashes: *const u8, pks: *const u8, codes: *mut i32, taken: *mut u8, group: *mut u32, max_groups: usize, n_groups: *mut u32, group_hashes: *mut u8, out_sigs: *mut u8, bitmaps: *mut u8, bitmap_len: usize, n_signed: *mut u32) -> i32;

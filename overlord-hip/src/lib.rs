@@ -228,6 +228,24 @@ impl HipCrypto {
         Ok(st)
     }
 
+    /// Capacity of the signature-point cache (`ovh_sig_cache_config`): the decompressed points of
+    /// signatures this context signed or verified with code 0, which `aggregate_signatures` sums
+    /// without decompressing them again. 0 disables and empties it; at most
+    /// `OVH_SIG_CACHE_MAX` entries.
+    pub fn sig_cache_config(&self, capacity: usize) -> Result<(), Box<dyn Error + Send>> {
+        check(unsafe { ffi::ovh_sig_cache_config(self.raw(), capacity) })
+    }
+
+    /// `ovh_agg_stats`: [sigma entries registered, entries now, aggregate_signatures calls on the
+    /// cache route, on the full path, their signatures not found in the cache,
+    /// verify_aggregated_signature calls on the table route, of those on a message-cache H, on
+    /// the full path].
+    pub fn agg_stats(&self) -> Result<[u64; 8], Box<dyn Error + Send>> {
+        let mut st = [0u64; 8];
+        check(unsafe { ffi::ovh_agg_stats(self.raw(), st.as_mut_ptr()) })?;
+        Ok(st)
+    }
+
     /// hash(rlp(Vote)) of n votes on the device (`ovh_vote_digests`: rlp + SM3 per vote, the
     /// bytes overlord signs, consensus.rs:169-175). `block_hashes` holds one hash per vote of at
     /// most OVH_VOTE_HASH_MAX bytes. Blocking.
