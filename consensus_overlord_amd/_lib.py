@@ -36,6 +36,9 @@ SIGNATURES = [
     ("ovh_aggregate_pks", ctypes.c_int, [_vp, _u8p, _szp, _sz, _u8p]),
     ("ovh_verify_aggregated", ctypes.c_int, [_vp, _u8p, _sz, _u8p, _sz, _u8p, _szp, _sz]),
     ("ovh_set_validators", ctypes.c_int, [_vp, _u8p, _sz]),
+    ("ovh_update_validators", ctypes.c_int, [_vp, _u8p, _sz, ctypes.POINTER(ctypes.c_uint64),
+                                            ctypes.POINTER(ctypes.c_uint32)]),
+    ("ovh_table_stats", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
     ("ovh_verify_batch", ctypes.c_int, [_vp, _sz, _u8p, _u8p, _u8p, _vp]),
     ("ovh_prefetch", ctypes.c_int, [_vp, _sz, _u8p, _u8p, _u8p]),
     ("ovh_cache_config", ctypes.c_int, [_vp, _sz]),

@@ -162,14 +162,38 @@ class ConsensusCrypto:
         with open(path) as fh:
             return cls(bytes.fromhex(fh.read().strip()), **kw)
 
-    def update_pubkeys(self, new_pubkeys: Sequence[bytes]) -> None:
+    def update_pubkeys(self, new_pubkeys: Sequence[bytes], keep_rounds: bool = False) -> Optional[List[int]]:
         """consensus.rs:361-363 (callers :131-136, :622-629): the validator keys, 48-byte
-        compressed, in config order -> the device validator table (ovh_set_validators)."""
+        compressed, in config order -> the device validator table (ovh_set_validators), which
+        closes every open round.
+        keep_rounds=True (ovh_update_validators), for the call on every committed block: nothing
+        happens when the list is the one the table holds; else only the keys new to the table are
+        checked again, and every open round that has taken no vote of a dropped key is carried
+        over to the new table (its Round goes on as a fresh round on the new table would after the
+        same taken votes). Returns the ids of the rounds the update closed (Round.id)."""
         keys = [bytes(p) for p in new_pubkeys]
         if any(len(k) != 48 for k in keys):
             raise Other("lose public key")
+        if not keep_rounds:
+            self.pubkeys = keys
+            raise_for(self.lib.ovh_set_validators(self.ctx.ptr, b"".join(keys), len(keys)))
+            return None
+        closed = (ctypes.c_uint64 * self.ROUNDS_MAX)()
+        n_closed = ctypes.c_uint32(0)
+        raise_for(self.lib.ovh_update_validators(self.ctx.ptr, b"".join(keys), len(keys), closed, ctypes.byref(n_closed)))
         self.pubkeys = keys
-        raise_for(self.lib.ovh_set_validators(self.ctx.ptr, b"".join(keys), len(keys)))
+        return [int(closed[k]) for k in range(int(n_closed.value))]
+
+    TABLE_NSTATS = 8           # include/ovhip.h OVH_TABLE_NSTATS
+
+    def table_stats(self):
+        """(ovh_set_validators calls, keep_rounds updates that found the list unchanged, ... that
+        rebuilt the table, keys those sent through the decompression and subgroup check, keys they
+        carried over, rounds they carried over, rounds they closed, table entries now) since the
+        context was created (ovh_table_stats)."""
+        st = (ctypes.c_uint64 * self.TABLE_NSTATS)()
+        raise_for(self.lib.ovh_table_stats(self.ctx.ptr, st))
+        return tuple(int(x) for x in st)
 
     def scalar(self) -> bytes:
         """The 32-byte scalar the private key parses to (ovh_sk_parse)."""
@@ -623,16 +647,21 @@ class Round:
     hash, added as they arrive. For any cut of a vote list into consecutive adds the codes, the
     taken flags, the count, the bitmap and the aggregated signature equal build_qc's over the
     whole list. Use as a context manager, or close() it; update_pubkeys closes it as well (every
-    later call then raises ValueError)."""
+    later call then raises ValueError), and so does update_pubkeys(keep_rounds=True) when it returns
+    the round's id; a round that call carries over goes on with the new table's bitmap length."""
 
     def __init__(self, crypto: ConsensusCrypto, hash_: bytes):
         self.crypto = crypto
         self.lib = crypto.lib
         self.hash = bytes(hash_)
-        self.bitmap_len = (len(crypto.pubkeys) + 7) // 8
         rid = ctypes.c_uint64(0)
         raise_for(self.lib.ovh_round_open(crypto.ctx.ptr, self.hash, len(self.hash), ctypes.byref(rid)))
         self.id: Optional[int] = int(rid.value)
+
+    @property
+    def bitmap_len(self) -> int:
+        """ceil(n / 8) of the table the round is on now (a carried round follows the update)"""
+        return (len(self.crypto.pubkeys) + 7) // 8
 
     def _id(self) -> int:
         if self.id is None:

@@ -53,6 +53,7 @@
 #include "proof.hpp"
 #include "qc_round_groups.hpp"
 #include "qc_segments.hpp"
+#include "tab_diff.hpp"
 #include "sig_cache.hpp"
 #include "rlp.hpp"
 #include "sm3.hpp"
@@ -1212,6 +1213,7 @@ __global__ __launch_bounds__(64) void k_vm_signg(uint32_t n, VmDev p0, VmDev p1,
 
 #include "msm.hpp"
 #include "qc.hpp"
+#include "tab_update.hpp"
 
 // Validator table (ovh_set_validators) and the keys of verify_aggregated_signature: one 48-byte
 // compressed key per 16-lane slice (program "pkchk": decompression + G1 subgroup check) -> flags
@@ -1730,6 +1732,7 @@ struct ovh_ctx {
   // RLC coefficients: fresh getrandom seed per batch, or the test seed (OVH_FLAG_TEST_RLC)
   uint64_t test_seed = 0, test_base = 0;
   ValidatorTable tab;
+  uint64_t tstat[OVH_TABLE_NSTATS] = {};  // ovh_table_stats ([7], the entries now, is tab.n); under mu
   std::vector<QcRound> rounds;  // open rounds, at most OVH_ROUNDS_MAX (a multi context's: on sub[0])
   uint64_t round_next = 1;      // ids are never reused
   // ovh_round_add of up to small_max votes: sigma of the add's votes from a sigchk launch on
@@ -5019,6 +5022,7 @@ int ovh_set_validators(ovh_ctx* c, const uint8_t* pks, size_t n) {
       CHK(set_validators_locked(s, pks, n));
     }
     std::lock_guard<std::mutex> g(c->mu);
+    ++c->tstat[0];
     c->tab.n = (uint32_t)n;
     c->tab.keys = c->sub[0]->tab.keys;
     c->tab.hflags = c->sub[0]->tab.hflags;
@@ -5026,7 +5030,157 @@ int ovh_set_validators(ovh_ctx* c, const uint8_t* pks, size_t n) {
     return 0;
   }
   std::lock_guard<std::mutex> g(c->mu);
+  ++c->tstat[0];
   return set_validators_locked(c, pks, n);
+}
+
+// ovh_update_validators. The launch code of the two kernels of
+// tab_update.hpp, shared with the test probe (tests/device/tab_probe.hip).
+static void enqueue_tab_build(hipStream_t st, uint32_t n, const uint32_t* dsrc, Slab old, const uint32_t* old_flags,
+                              Slab fresh, const uint32_t* fresh_flags, Slab out, uint32_t* out_flags) {
+  if (n) k_tab_build<<<nblk(n), WG, 0, st>>>(n, dsrc, old, old_flags, fresh, fresh_flags, out, out_flags);
+}
+// span: the largest tn, old or new, of the K rounds; lost: K words, zero before the launch
+static void enqueue_round_remap(hipStream_t st, uint32_t K, uint32_t span, const TabRoundRef* drefs, const uint32_t* drsrc,
+                                const uint32_t* ddst, const uint32_t* dsorted, uint32_t* dlost) {
+  constexpr uint32_t TAIL = 6 * 12 + 96 / 4;  // R and the 96 bytes: a lane per word
+  if (K) k_round_remap<<<dim3(nblk(span > TAIL ? span : TAIL), K), WG, 0, st>>>(drefs, drsrc, ddst, dsorted, dlost);
+}
+static_assert(sizeof(TabRoundRef) == 32 && OVH_TABLE_NSTATS == 8, "staged as 8 words; the counters of ovh_table_stats");
+
+// Device allocations of an update until they become the table's or a round's: an error frees them.
+struct TabMem {
+  std::vector<void*> p;
+  ~TabMem() {
+    for (void* q : p)
+      if (q) (void)hipFree(q);
+  }
+  int get(uint32_t** out, size_t words) {
+    void* q = nullptr;
+    if (hipMalloc(&q, (words ? words : 1) * 4) != hipSuccess) return OVH_ERR_DEVICE;
+    p.push_back(q);
+    *out = (uint32_t*)q;
+    return 0;
+  }
+  void keep(void* q) {
+    for (void*& x : p)
+      if (x == q) x = nullptr;
+  }
+};
+
+// The changed-list path on one device (caller holds c->mu; d is the diff of c->tab.keys against
+// pks, not `same`; the context has a table). Build, then swap: an error before the swap leaves the
+// table and every round as they were. closed: the ids of the rounds that took a vote of a dropped
+// key; *carried: the rounds that moved to the new table.
+static int update_validators_locked(ovh_ctx* c, const uint8_t* pks, size_t n, const TabDiff& d, std::vector<uint64_t>& closed,
+                                    uint32_t* carried) {
+  HIPCHK(hipSetDevice(c->device));
+  CHK(sync_all(c));  // the pool's vote_t reads the planes; a round's words may be in an add's pass
+  ValidatorTable& t = c->tab;
+  const uint32_t N = (uint32_t)n, no = t.n, m = (uint32_t)d.fresh.size(), K = N ? (uint32_t)c->rounds.size() : 0;
+  if (N == 0) {  // nothing to build: every round is closed, the allocation stays (as ovh_set_validators)
+    for (const QcRound& r : c->rounds) {
+      closed.push_back(r.id);
+      (void)hipFree(r.dev);
+    }
+    c->rounds.clear();
+  } else {
+    uint32_t cap = 64;
+    while (cap < N) cap <<= 1;
+    if (cap < t.cap) cap = t.cap;  // as ovh_set_validators: the table never shrinks
+    const uint32_t mcap = (m + 63) / 64 * 64, bw = (N + 31) / 32;
+    TabMem mem;
+    uint32_t *planes, *flags, *qc, *fresh = nullptr, *maps, *rdev[OVH_ROUNDS_MAX] = {};
+    CHK(mem.get(&planes, (size_t)3 * 12 * cap));
+    CHK(mem.get(&flags, cap));
+    CHK(mem.get(&qc, (size_t)2 * cap + cap / 32 + 1));
+    for (uint32_t k = 0; k < K; ++k) CHK(mem.get(&rdev[k], QcRound::words(N, bw)));
+    // maps, one upload: round references (8 words each) | lost | src | rsrc | sorted | dst
+    const size_t o_lost = (size_t)8 * K, o_src = o_lost + K, o_rsrc = o_src + N, o_sorted = o_rsrc + N, o_dst = o_sorted + N;
+    std::vector<uint32_t> hm(o_dst + no, 0), hf(m), hlost(K, 0);
+    for (uint32_t k = 0; k < K; ++k) {
+      const QcRound& r = c->rounds[k];
+      const TabRoundRef ref{r.dev, rdev[k], r.tn, r.bw, N, bw};
+      memcpy(&hm[(size_t)8 * k], &ref, sizeof ref);
+    }
+    std::copy(d.src.begin(), d.src.end(), hm.begin() + o_src);
+    std::copy(d.rsrc.begin(), d.rsrc.end(), hm.begin() + o_rsrc);
+    std::copy(d.sorted.begin(), d.sorted.end(), hm.begin() + o_sorted);
+    std::copy(d.dst.begin(), d.dst.end(), hm.begin() + o_dst);
+    CHK(mem.get(&maps, hm.size()));
+    std::vector<uint8_t> hk((size_t)48 * m);  // the keys new to the table, compacted
+    // the stream copies from / into the vectors above: an error return waits for it first
+    struct Drain {
+      hipStream_t s;
+      bool armed;
+      ~Drain() {
+        if (armed) (void)hipStreamSynchronize(s);
+      }
+    } drain{c->stream, true};
+    if (m) {  // only they are decompressed and subgroup-checked, into a slab of their own
+      CHK(mem.get(&fresh, (size_t)(3 * 12 + 1) * mcap));
+      for (uint32_t j = 0; j < m; ++j) memcpy(&hk[(size_t)48 * j], pks + (size_t)48 * d.fresh[j], 48);
+      CHK(ensure_in(c, hk.size() + 64));
+      HIPCHK(hipMemcpyAsync(c->in_buf, hk.data(), hk.size(), hipMemcpyHostToDevice, c->stream));
+      constexpr uint32_t PK_SL = 64 / VM_PKCHK_W;
+      k_vm_pkchk<<<(m + PK_SL - 1) / PK_SL, 64, LDS_PKCHK, c->stream>>>(m, c->vm_pkchk, c->vm_consts, c->in_buf,
+                                                                        Slab{fresh, mcap}, fresh + (size_t)3 * 12 * mcap);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(hf.data(), fresh + (size_t)3 * 12 * mcap, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipMemcpyAsync(maps, hm.data(), hm.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(qc + cap, d.rank.data(), (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
+    enqueue_tab_build(c->stream, N, maps + o_src, Slab{t.planes, t.cap}, t.flags, Slab{fresh, mcap},
+                      fresh ? fresh + (size_t)3 * 12 * mcap : nullptr, Slab{planes, cap}, flags);
+    if (K) {
+      enqueue_round_remap(c->stream, K, std::max(no, N), (const TabRoundRef*)maps, maps + o_rsrc, maps + o_dst,
+                          maps + o_sorted, maps + o_lost);
+      HIPCHK(hipMemcpyAsync(hlost.data(), maps + o_lost, (size_t)K * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));  // the one wait: the new keys' flags, the rounds' lost words
+    drain.armed = false;
+    // the swap: nothing below fails
+    std::vector<uint32_t> hflags(N);
+    for (uint32_t i = 0; i < N; ++i) hflags[i] = (d.src[i] & TAB_NEW) ? hf[d.src[i] & ~TAB_NEW] : t.hflags[d.src[i]];
+    for (void* p : {(void*)t.planes, (void*)t.flags, (void*)t.qc})
+      if (p) (void)hipFree(p);
+    t.planes = planes;
+    t.flags = flags;
+    t.qc = qc;
+    t.cap = cap;
+    for (uint32_t* p : {planes, flags, qc}) mem.keep(p);
+    t.hflags.swap(hflags);
+    std::vector<QcRound> open;
+    for (uint32_t k = 0; k < K; ++k) {
+      QcRound r = c->rounds[k];
+      (void)hipFree(r.dev);
+      if (hlost[k]) {  // R holds the dropped voter's signature and cannot lose it
+        closed.push_back(r.id);
+        continue;     // (its new allocation goes with `mem`)
+      }
+      r.dev = rdev[k];
+      r.tn = N;
+      r.bw = bw;
+      mem.keep(rdev[k]);
+      open.push_back(r);
+    }
+    c->rounds.swap(open);
+    *carried += (uint32_t)c->rounds.size();
+  }
+  if (t.qcg) (void)hipFree(t.qcg);  // sized by the old table; ensure_qcg allocates it again
+  t.qcg = nullptr;
+  t.qcg_words = 0;
+  t.keys.clear();
+  t.index.clear();
+  if (N == 0) t.hflags.clear();
+  for (size_t i = 0; i < n; ++i) {
+    t.keys.emplace_back((const char*)pks + 48 * i, 48);
+    t.index.emplace(t.keys.back(), (uint32_t)i);  // keeps the first of duplicate keys
+  }
+  t.sorted = d.sorted;
+  t.n = N;
+  return 0;
 }
 
 int ovh_verify_batch(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* hashes, const uint8_t* pks,
@@ -6309,6 +6463,52 @@ struct DeviceGuard {
     if (dev >= 0) (void)hipSetDevice(dev);
   }
 };
+
+// ovh_update_validators (update_validators_locked is beside
+// set_validators_locked): every device's lock for the whole call, as the other multi-device entry points.
+int ovh_update_validators(ovh_ctx* c, const uint8_t* pks, size_t n, uint64_t* closed, uint32_t* n_closed) {
+  if (!c || (n && !pks) || n > (1u << 20)) return OVH_ERR_ARG;
+  DeviceGuard dg;
+  auto locks = lock_all(c);
+  TabDiff d;
+  tab_diff(c->tab.keys, pks, n, d);
+  if (d.same) {  // the every-block case: no HIP call, no stream waited for, no round touched
+    ++c->tstat[1];
+    if (n_closed) *n_closed = 0;
+    return 0;
+  }
+  const std::vector<ovh_ctx*> devs = devices_of(c);
+  std::vector<uint64_t> gone;
+  uint32_t carried = 0;
+  if (!devs[0]->tab.planes) {  // no table yet (and so no round): this is ovh_set_validators
+    for (ovh_ctx* s : devs) CHK(set_validators_locked(s, pks, n));
+    c->tstat[3] += n;
+  } else {
+    for (ovh_ctx* s : devs) CHK(update_validators_locked(s, pks, n, d, gone, &carried));
+    c->tstat[3] += d.fresh.size();
+    c->tstat[4] += d.kept;
+  }
+  if (!c->sub.empty()) {
+    c->tab.n = (uint32_t)n;
+    c->tab.keys = c->sub[0]->tab.keys;
+    c->tab.hflags = c->sub[0]->tab.hflags;
+    c->tab.sorted = c->sub[0]->tab.sorted;
+  }
+  ++c->tstat[2];
+  c->tstat[5] += carried;
+  c->tstat[6] += gone.size();
+  if (closed) std::copy(gone.begin(), gone.end(), closed);
+  if (n_closed) *n_closed = (uint32_t)gone.size();
+  return 0;
+}
+
+int ovh_table_stats(ovh_ctx* c, uint64_t stats[8]) {
+  if (!c || !stats) return OVH_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  for (int k = 0; k < OVH_TABLE_NSTATS - 1; ++k) stats[k] = c->tstat[k];
+  stats[OVH_TABLE_NSTATS - 1] = c->tab.n;
+  return 0;
+}
 
 int ovh_verify_batch_async(ovh_ctx* c, size_t n, const uint8_t* sigs, const uint8_t* hashes, const uint8_t* pks,
                            int32_t* codes) {

@@ -50,6 +50,7 @@ for a choke; `hash` is Crypto::hash (SM3, util.rs:83-87).
 """
 from __future__ import annotations
 
+import inspect
 import logging
 import time
 from dataclasses import dataclass
@@ -321,9 +322,31 @@ class VoteIngress:
         while self.rounds:
             self.rounds.popitem()[1].close()
 
+    def update_pubkeys(self, keys) -> None:
+        """The node's update_pubkeys on every committed block (consensus.rs:622-629), with the
+        rounds of the next height already open. rounds=True and a crypto whose update_pubkeys
+        takes keep_rounds: the update keeps the device table and the rounds (nothing happens for
+        the list of the block before), and exactly the rounds whose ids it returns as closed --
+        those that took a vote of a dropped validator -- are forgotten here. Otherwise every round
+        is closed first, then the plain update."""
+        if self.use_rounds and _takes_keep_rounds(self.crypto):
+            closed = set(self.crypto.update_pubkeys(keys, keep_rounds=True) or ())
+            for h in [h for h, r in self.rounds.items() if r.id in closed]:
+                self.rounds.pop(h).close()
+            return
+        self.close_rounds()
+        self.crypto.update_pubkeys(keys)
+
     def _send(self, kind, msg) -> None:
         self.stats["forwarded"] += 1
         self.forward(kind, msg)
+
+
+def _takes_keep_rounds(crypto) -> bool:
+    try:
+        return "keep_rounds" in inspect.signature(crypto.update_pubkeys).parameters
+    except (AttributeError, TypeError, ValueError):
+        return False
 
 
 def overlord_verify(crypto, kind: str, msg) -> None:

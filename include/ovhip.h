@@ -179,6 +179,41 @@ int ovh_verify_aggregated(ovh_ctx* ctx, const uint8_t* agg_sig, size_t agg_len, 
  * not parse are kept (their votes answer 102, as the reference's per-call parse would). */
 int ovh_set_validators(ovh_ctx* ctx, const uint8_t* pks, size_t n);
 
+/* ConsensusCrypto::update_pubkeys for a node that keeps rounds open across commits. The reference
+ * calls update_pubkeys on every committed block (Brain::commit), almost always with the list of the
+ * block before, while the rounds of the next height are already open.
+ * The table: every later call of the context that reads the validator table returns the same bytes
+ * and codes as after ovh_set_validators(ctx, pks, n). A key's point and flags depend only on its 48
+ * bytes, so they are copied from the old table, also for keys that do not parse or lie outside G1.
+ *   Identical list (same n, bytes and order): returns 0 after a host comparison under the context
+ *   mutex. No device call, no stream is waited for (batches in flight included), no round is touched.
+ *   Changed list (any other, a permutation included): waits for the context's streams as
+ *   ovh_set_validators does; only the keys whose bytes the old table does not hold are decompressed
+ *   and subgroup-checked; the new table is built beside the old one and then swapped in.
+ * Open rounds: a round is carried over when every voter it has taken is a key of the new list. It
+ * keeps its id, hash, count, sum and budget. The defining property: let T be the votes it has taken
+ * so far, in order; from the call on, n_signed, the bitmap (new length ceil(n / 8), new key order)
+ * and the 96 bytes are those of a fresh round on the new table to which T was added, and so after
+ * any further adds, for the codes and the taken flags of the new votes as well. A voter taken
+ * before is still not taken twice, a key new to the table can be taken from then on, an invalid
+ * vote still blocks nobody. A round that has taken a vote of a key the new list drops is closed
+ * (its sum holds that signature), and every round is when n == 0: its id is written to closed[]
+ * and is unknown from then on, as after ovh_round_close. *n_closed gets their number.
+ * On a context without a table the call is ovh_set_validators. A multi-device context updates every
+ * device's table; its rounds live on the first device. OVH_ERR_ARG (NULL context, NULL pks with
+ * n > 0, n > 2^20) changes and writes nothing. */
+int ovh_update_validators(ovh_ctx* ctx, const uint8_t* pks /* n x 48 */, size_t n,
+                          uint64_t* closed /* OVH_ROUNDS_MAX ids, may be NULL */,
+                          uint32_t* n_closed /* may be NULL */);
+
+/* Counters of the validator table since ovh_create: [0] ovh_set_validators calls, [1] update calls
+ * that found the list unchanged, [2] update calls that rebuilt the table, [3] keys that updates
+ * sent through the decompression and subgroup check, [4] keys that updates carried over, [5] rounds
+ * carried over by rebuilding updates, [6] rounds closed by updates, [7] table entries now.
+ * OVH_ERR_ARG for a NULL context or NULL stats, which writes nothing. */
+#define OVH_TABLE_NSTATS 8
+int ovh_table_stats(ovh_ctx* ctx, uint64_t stats[8] /* OVH_TABLE_NSTATS */);
+
 /* Batched verify_signature over n votes (fixed-size compressed encodings):
  * sigs n x 96 B, hashes n x 32 B, pks n x 48 B -> codes[n], codes[i] == the ovh_verify result
  * for vote i. One random-linear-combination check with secret 64-bit coefficients (a fresh

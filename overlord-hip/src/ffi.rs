@@ -42,6 +42,7 @@ pub const OVH_SIG_CACHE_DEFAULT: usize = 4096;
 pub const OVH_SIG_CACHE_MAX: usize = 65536;
 pub const OVH_ROUNDS_MAX: usize = 16;
 pub const OVH_ROUND_VOTES_MAX: usize = 1 << 24;
+pub const OVH_TABLE_NSTATS: usize = 8;
 
 extern "C" {
     pub fn ovh_create(device: i32, dst: *const u8, dst_len: usize, flags: u32) -> *mut OvhCtx;
@@ -64,6 +65,8 @@ extern "C" {
     pub fn ovh_aggregate_pks(ctx: *mut OvhCtx, pks: *const u8, pk_lens: *const usize, n: usize, out: *mut u8) -> i32;
     pub fn ovh_verify_aggregated(ctx: *mut OvhCtx, agg_sig: *const u8, agg_len: usize, hash: *const u8, hash_len: usize, pks: *const u8, pk_lens: *const usize, n: usize) -> i32;
     pub fn ovh_set_validators(ctx: *mut OvhCtx, pks: *const u8, n: usize) -> i32;
+    pub fn ovh_update_validators(ctx: *mut OvhCtx, pks: *const u8, n: usize, closed: *mut u64, n_closed: *mut u32) -> i32;
+    pub fn ovh_table_stats(ctx: *mut OvhCtx, stats: *mut u64) -> i32;
     pub fn ovh_verify_batch(ctx: *mut OvhCtx, n: usize, sigs: *const u8, hashes: *const u8, pks: *const u8, codes: *mut i32) -> i32;
     pub fn ovh_prefetch(ctx: *mut OvhCtx, n: usize, sigs: *const u8, hashes: *const u8, pks: *const u8) -> i32;
     pub fn ovh_cache_config(ctx: *mut OvhCtx, capacity: usize) -> i32;

@@ -190,6 +190,50 @@ impl HipCrypto {
         *self.pubkeys.write().await = keys;
     }
 
+    /// `update_pubkeys` for a node that keeps rounds open across commits (`ovh_update_validators`),
+    /// for the call on every committed block (consensus.rs:622-629): nothing happens when the list
+    /// is the one the table holds; else only the keys new to the table are checked again, and every
+    /// open round that has taken no vote of a dropped key is carried over to the new table. Returns
+    /// the ids of the rounds the update closed (their later calls return `CryptoErr(OVH_ERR_ARG)`);
+    /// keys that are not 48 bytes long empty the table as `update_pubkeys` does, which closes every
+    /// round (their `Round`s then answer `OVH_ERR_ARG` as well).
+    pub async fn update_pubkeys_keep_rounds<K: ophelia::PublicKey>(&self, new_pubkeys: Vec<K>) -> Vec<u64> {
+        let keys: Vec<Bytes> = new_pubkeys.iter().map(|k| k.to_bytes()).collect();
+        let ctx = self.ctx.clone();
+        let n = keys.len();
+        let all48 = keys.iter().all(|k| k.len() == 48);
+        let flat: Vec<u8> = keys.iter().flat_map(|k| k.iter().copied()).collect();
+        let (code, closed) = tokio::task::spawn_blocking(move || {
+            let mut ids = [0u64; ffi::OVH_ROUNDS_MAX];
+            let mut cnt = 0u32;
+            let c = if all48 {
+                unsafe { ffi::ovh_update_validators(ctx.0, flat.as_ptr(), n, ids.as_mut_ptr(), &mut cnt) }
+            } else {
+                let c = unsafe { ffi::ovh_update_validators(ctx.0, std::ptr::null(), 0, ids.as_mut_ptr(), &mut cnt) };
+                if c == ffi::OVH_OK {
+                    ffi::OVH_ERR_PUBKEY
+                } else {
+                    c
+                }
+            };
+            (c, ids[..cnt as usize].to_vec())
+        })
+        .await
+        .unwrap_or((ffi::OVH_ERR_DEVICE, Vec::new()));
+        self.table_error.store(code, Ordering::Relaxed);
+        *self.pubkeys.write().await = keys;
+        closed
+    }
+
+    /// `ovh_table_stats`: [`ovh_set_validators` calls, updates that found the list unchanged,
+    /// updates that rebuilt the table, keys those checked again, keys they carried over, rounds
+    /// they carried over, rounds they closed, table entries now].
+    pub fn table_stats(&self) -> Result<[u64; ffi::OVH_TABLE_NSTATS], Box<dyn Error + Send>> {
+        let mut st = [0u64; ffi::OVH_TABLE_NSTATS];
+        check(unsafe { ffi::ovh_table_stats(self.raw(), st.as_mut_ptr()) })?;
+        Ok(st)
+    }
+
     /// The code of the last failed `update_pubkeys` upload (0 when the table is current).
     pub fn table_error(&self) -> i32 {
         self.table_error.load(Ordering::Relaxed)
